@@ -6,17 +6,25 @@ system), the whole post-order partial-likelihood traversal (n-2 site-updates per
 the scalar back on the host -- everything the reference's Lk(NULL) does (src/lk.c:443-649), inputs resident in HBM.
 
   --gpus 1            BASELINE configs[1] (cfg2: 100 taxa x 50 000 nt patterns, GTR+G4) on one MI355X; the JSON line
-                      also carries `roofline`, `cpu_baseline` (real PhyML AVX, 1 host core, same box, same run) and,
-                      under `extra`, the 20-state configuration (cfg3: 200 taxa x 10 000 aa patterns, LG+G4) and
-                      `call_latency`: microseconds per SPR regraft candidate / per scalar-returning call of a seeded
-                      SPR + Br_Len_Opt call stream at the cfg5 size and at the reference's example-alignment size.
+                      also carries `roofline` (from the timed launches' own counters).  With --full it also carries the
+                      all-buffers-stored companion, the measured HBM streams (membench), `cpu_baseline` (real PhyML AVX,
+                      1 host core, same box, same run) and, under `extra`, the 20-state configuration (cfg3: 200 taxa x
+                      10 000 aa patterns, LG+G4), cfg4 on one GPU and `call_latency`: microseconds per SPR regraft
+                      candidate / per scalar-returning call of a seeded SPR + Br_Len_Opt call stream at the cfg5 size and
+                      at the reference's example-alignment size.
   --gpus N (N > 1)    BASELINE configs[3] (cfg4: 100 taxa x 1 000 000 nt patterns), STRONG scaling: contiguous pattern
                       shards of 1e6/N per GPU, ONE RCCL all-reduce of {warning, lnL} per evaluation inside libphyhip.so.
                       Launched by the driver as N ranks (torch.distributed.run, WORLD_SIZE = N): one process per GPU,
                       phyhip_comm_init_rank on an id broadcast through torch.distributed (gloo: rendezvous, barrier and the
                       MAX over the ranks' timers are host-side; the only RCCL communicator is the library's own).  Launched bare
                       (`python bench.py --gpus N`): ONE process drives all N devices through the sharded instance of
-                      the C ABI (phyhip_create_instance with a resource list of N devices, ncclCommInitAll).
+                      the C ABI (phyhip_create_instance with a resource list of N devices, ncclCommInitAll).  With --full
+                      the same patterns also run whole on one GPU (`strong_scaling`).
+  --full              everything beyond the headline (above); a plain run sets up, warms up, times --steps steps and
+                      prints the line.
+  --dump-outputs DIR  after the timed steps, what the last step left for a caller of Lk(NULL), as float64 .npy files:
+                      lnL, and per pattern c_lnL_sorted, cur_site_lk, unscaled_site_lk_cat, fact_sum_scale (a fixed,
+                      seeded sample of the patterns, `pattern_index.npy`, when the whole would pass 64 MB).
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -244,6 +252,33 @@ def timed_steps(t, steps, warmup, sync, barrier=None):
     return time.perf_counter() - t0, lnl
 
 
+DUMP_LIMIT = 64 << 20  # bytes of all the files of --dump-outputs together
+
+
+def site_arrays(t):
+    """What Lk(NULL) leaves for its caller besides the scalar (src/lk.c:855-857): per pattern c_lnL_sorted, cur_site_lk,
+    unscaled_site_lk_cat ([pattern][category]) and fact_sum_scale, as float64 (the scale exponents are small integers: exact)."""
+    a, b, c, f = t.inst.site_outputs()
+    return {"c_lnL_sorted": a, "cur_site_lk": b, "unscaled_site_lk_cat": c, "fact_sum_scale": f.astype(np.float64)}
+
+
+def dump_outputs(d, lnl, sites):
+    """--dump-outputs: lnL and the per-pattern arrays as DIR/<name>.npy; beyond DUMP_LIMIT, the same fixed, seeded sample of
+    patterns from every array (its indices in pattern_index.npy)."""
+    os.makedirs(d, exist_ok=True)
+    out = {"lnL": np.array([lnl], dtype=np.float64)}
+    P = len(sites["c_lnL_sorted"])
+    per_pattern = sum(v.nbytes for v in sites.values()) / P
+    room = DUMP_LIMIT - 4096  # (the .npy headers)
+    if per_pattern * P > room:
+        idx = np.sort(np.random.default_rng(12345).choice(P, int(room // (per_pattern + 8)), replace=False))
+        sites = {k: v[idx] for k, v in sites.items()}
+        out["pattern_index"] = idx.astype(np.float64)
+    out.update(sites)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def roofline_block(t, n, P, S, C, workload_key, with_traffic, shards=1):
     """SURVEY 8(d) figure (algorithmic bytes / kernel time) plus the honest companions: the traffic model of the launch
     (results written once, children read unless forwarded in registers or tips), the write stream alone, and -- when a
@@ -287,7 +322,8 @@ def roofline_block(t, n, P, S, C, workload_key, with_traffic, shards=1):
 
 
 def run_single(args, torch):
-    """N = 1: cfg2 on cuda:0 (the line BENCH records), cfg3 under `extra`."""
+    """N = 1: cfg2 on cuda:0 (the line BENCH records); with --full also cfg3 / cfg4 / call_latency under `extra`, the companions and
+    the CPU baseline."""
     from phyml_amd import synth, workloads
     torch.cuda.set_device(0)
     wl = workloads.make(args.workload, n_pattern=args.patterns)
@@ -297,7 +333,9 @@ def run_single(args, torch):
     dt, lnl = timed_steps(t, args.steps, args.warmup, torch.cuda.synchronize)
     value = float(P) * (n - 2) * args.steps / dt / 1e6
     roof, kdur = roofline_block(t, n, P, S, C, args.workload, args.patterns is None)
-    if roof["virtual_buffers"]["virtual_after_launch"] > 0 and not args.no_companion:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lnl, site_arrays(t))
+    if args.full and roof["virtual_buffers"]["virtual_after_launch"] > 0 and not args.no_companion:
         roof["all_buffers_stored"] = all_stored_companion(wl, args, torch, n, P)
         try:
             roof["materialise"] = materialise_after_traversal(wl, torch)
@@ -313,7 +351,7 @@ def run_single(args, torch):
            "lnL": lnl, "roofline": roof}
     if S == 20:
         out["mfma"] = mfma_block(P, C, n, kdur)
-    mr = measured_roofline()
+    mr = measured_roofline() if args.full else None
     if mr:
         roof["measured_read_GBps"] = mr["read_GBps"]
         roof["measured_write_GBps"] = mr["write_GBps"]
@@ -340,7 +378,7 @@ def run_single(args, torch):
         if "checksum" in exp:
             out["input_checksum_ok"] = bool(synth.states_checksum(st) == exp["checksum"])
     t.close()
-    if not args.no_extra and args.workload == "cfg2_nt_100x50k" and args.patterns is None:
+    if args.full and not args.no_extra and args.workload == "cfg2_nt_100x50k" and args.patterns is None:
         out["extra"] = {"cfg3_aa_200x10k": extra_line("cfg3_aa_200x10k", args, torch)}
         # the strong-scaling reference of the N > 1 lines (cfg4, 100 taxa x 1 M patterns) on THIS one GPU, same protocol: a
         # 1 -> 8 curve over one workload is value(N > 1) against this value, whatever the N = 1 headline workload is
@@ -353,7 +391,7 @@ def run_single(args, torch):
                 out["extra"]["call_latency"] = call_latency()
             except Exception as e:  # (an extra must never cost the run its headline line)
                 out["extra"]["call_latency"] = {"error": repr(e)}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(wl, args.cpu_sample, args.cpu_reps)
     return out
 
@@ -589,6 +627,12 @@ def run_sharded(args, torch):
         every = [mine]  # (one process, sharded instance: the slowest shard's kernel, the first device's collective path)
     per_rank = {"kernel_us": [e["kernel_us"] for e in every], "collective_us": [e["collective_us"] for e in every],
                 "comm_size": [e["comm_size"] for e in every], "patterns": [e["patterns"] for e in every]}
+    sites = site_arrays(t) if args.dump_outputs else None
+    if sites is not None and multiproc:  # (rank 0 writes the whole alignment's arrays: the ranks' shards in rank order)
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(sites, parts, dst=0)
+        if rank == 0:
+            sites = {k: np.concatenate([p[k] for p in parts]) for k in sites}
     t.close()
     out = None
     if rank == 0:
@@ -606,7 +650,9 @@ def run_sharded(args, torch):
         if exp and total == exp["n_pattern"]:
             out["lnL_reference_avx"] = exp["lnL"]
             out["lnL_rel_err"] = abs(lnl - exp["lnL"]) / abs(exp["lnL"])
-        if not args.no_extra:
+        if sites is not None:
+            dump_outputs(args.dump_outputs, lnl, sites)
+        if args.full and not args.no_extra:
             # the strong-scaling reference: the same 1 M patterns on ONE of these GPUs, same protocol, same run
             wl1 = workloads.make(name, n_pattern=total)
             t1 = build_tree(wl1, device=local if multiproc else 0)
@@ -719,6 +765,11 @@ def main():
                     help="skip the all-buffers-stored companion run (counter profiles: its launches share the traversal kernel's name)")
     ap.add_argument("--cpu-sample", type=int, default=50000)
     ap.add_argument("--cpu-reps", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beyond the headline: all-stored companion, membench streams, CPU baseline, "
+                         "cfg3 / cfg4 / call_latency under `extra` (N = 1), the single-GPU strong-scaling reference (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (lnL and the per-pattern outputs) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     global VIRTUAL
     VIRTUAL = args.virtual_buffers

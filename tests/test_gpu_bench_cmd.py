@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,7 @@ def _physical(r):
 
 
 def test_default_single_gpu_line():
-    d, lines = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
+    d, lines = _run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
     assert len(lines) == 1 and len(lines[0]) < 2000  # N = 1: nothing but the JSON line on stdout, short enough for a log tail
     for k in CONTRACT:
         assert k in d, k
@@ -81,9 +82,39 @@ def test_default_single_gpu_line():
     assert full["extra"]["call_latency"]["spr_37x429_aa"]["finite"]
 
 
-def test_bare_multi_gpu_command_with_two_shards_on_device_0():
-    d, _ = _run([sys.executable, "bench.py", "--gpus", "2", "--patterns", "200000", "--steps", "3", "--warmup", "1"],
-                {"PHYHIP_BENCH_DEVICES": "0,0"})
+def test_plain_single_gpu_line_and_its_outputs(tmp_path):
+    """The plain command (no --full): the headline workload alone -- set up, warm up, --steps timed steps, the line -- and, with
+    --dump-outputs, what the last timed Lk(NULL) left for its caller."""
+    out = tmp_path / "out"
+    d, lines = _run([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)], {})
+    assert len(lines) == 1 and len(lines[0]) < 2000
+    for k in CONTRACT:
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert d["n_gpus"] == 1 and d["scaling"] == "none" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["config"]["workload"] == "cfg2_nt_100x50k" and d["lnL_rel_err"] < 1e-6
+    _physical(d["roofline"])
+    for k in ("cpu_baseline", "cfg3_aa_200x10k", "cfg4_nt_100x1M_one_gpu", "call_us"):
+        assert k not in d, k
+    assert "all_stored_kernel_us" not in d["roofline"]
+    full = _detail()
+    assert full["input_checksum_ok"] and "extra" not in full and full["steps"] == 7
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert set(files) == {"lnL.npy", "c_lnL_sorted.npy", "cur_site_lk.npy", "unscaled_site_lk_cat.npy", "fact_sum_scale.npy"}
+    assert all(v.dtype == np.float64 for v in files.values())
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    lnl = files["lnL.npy"]
+    assert lnl.shape == (1,) and lnl[0] == full["lnL"]
+    site = files["c_lnL_sorted.npy"]
+    assert site.shape == (50000,) and abs(site.sum() - lnl[0]) < 1e-10 * abs(lnl[0])   # (every pattern weight is 1)
+    assert files["cur_site_lk.npy"].shape == (50000,) and files["unscaled_site_lk_cat.npy"].shape == (50000, 4)
+    f = files["fact_sum_scale.npy"]
+    assert f.shape == (50000,) and np.array_equal(f, np.round(f))
+
+
+def test_bare_multi_gpu_command_with_two_shards_on_device_0(tmp_path):
+    d, _ = _run([sys.executable, "bench.py", "--full", "--gpus", "2", "--patterns", "200000", "--steps", "3", "--warmup", "1",
+                 "--dump-outputs", str(tmp_path)], {"PHYHIP_BENCH_DEVICES": "0,0"})
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["steps"] == 3
@@ -95,13 +126,16 @@ def test_bare_multi_gpu_command_with_two_shards_on_device_0():
     ss = full["strong_scaling"]
     assert abs(full["lnL"] - ss["single_gpu_lnL"]) / abs(full["lnL"]) < 1e-10   # the sharded sum against the whole alignment on one GPU
     assert d["value"] > 0 and d["strong_scaling"]["single_gpu_value"] > 0
+    site = np.load(tmp_path / "c_lnL_sorted.npy")   # both shards' patterns, in order
+    assert site.shape == (200000,) and abs(site.sum() - full["lnL"]) < 1e-10 * abs(full["lnL"])
+    assert np.load(tmp_path / "lnL.npy")[0] == full["lnL"]
 
 
-def test_torchrun_form_one_rank():
+def test_torchrun_form_one_rank(tmp_path):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "bench.py", "--gpus", "1", "--patterns", "200000", "--steps", "3", "--warmup", "1"]
-    d, _ = _run(cmd, {"PHYHIP_BENCH_FORCE_DIST": "1"})
+           "--master-port", str(port), "bench.py", "--full", "--gpus", "1", "--patterns", "200000", "--steps", "3", "--warmup", "1"]
+    d, _ = _run(cmd + ["--dump-outputs", str(tmp_path)], {"PHYHIP_BENCH_FORCE_DIST": "1"})
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["scaling"] == "strong"
@@ -112,6 +146,8 @@ def test_torchrun_form_one_rank():
     assert "phyhip_comm_init_rank" in full["config"]["mode"]
     ss = full["strong_scaling"]
     assert abs(full["lnL"] - ss["single_gpu_lnL"]) / abs(full["lnL"]) < 1e-10
+    site = np.load(tmp_path / "c_lnL_sorted.npy")
+    assert site.shape == (200000,) and abs(site.sum() - full["lnL"]) < 1e-10 * abs(full["lnL"])
 
 
 def test_full_size_sharded_line_matches_the_reference_shard_sum():

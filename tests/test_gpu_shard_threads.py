@@ -6,6 +6,7 @@ sharded mixtures and the collective on a one-GPU box; with two or more devices t
 those first on a multi-GPU box, and runs here on the repeated list.)"""
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -139,5 +140,7 @@ def test_multigpu_selfcheck_runs_on_this_box():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "multigpu_selfcheck.py"), "--devices", devs, "--patterns", "200000", "--steps", "5"],
                        cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.rstrip().endswith("OK"), (r.stdout[-1500:], r.stderr[-1500:])
-    out = json.loads(r.stdout[:r.stdout.rindex("}") + 1])
+    # (RCCL may print a banner of its own on stdout in front of the document: the document starts at its own "{" line)
+    doc = r.stdout[:r.stdout.rindex("}") + 1]
+    out = json.loads(doc[re.search(r"^\{$", doc, re.M).start():])
     assert out["lnL_rel_err_vs_shard_sum"] < 1e-12 and out["rccl_ranks"] == len(set(devs.split(",")))

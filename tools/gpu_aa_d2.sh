@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_cases.py te
 for rep in 1 2 3; do
 for d2 in 1 0; do
   for pat in "" "--patterns 5000" "--patterns 25000"; do
-    PHYHIP_LIBDIR=phyml_amd/lib_diag PHYHIP_AA_D2=$d2 timeout 300 python bench.py --workload cfg3_aa_200x10k $pat --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $o/b.json 2> $o/b.err || tail -3 $o/b.err
+    PHYHIP_LIBDIR=phyml_amd/lib_diag PHYHIP_AA_D2=$d2 timeout 300 python bench.py --full --workload cfg3_aa_200x10k $pat --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $o/b.json 2> $o/b.err || tail -3 $o/b.err
     python - "$d2" "$pat" <<'P'
 import json,sys
 d=json.load(open('bench_detail.json')); r=d['roofline']

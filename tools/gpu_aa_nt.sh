@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_cases.py te
 for rep in 1 2; do
 for nt in 1 2; do
   for pat in "" "--patterns 100000"; do
-    PHYHIP_LIBDIR=phyml_amd/lib_diag PHYHIP_AA_NT=$nt timeout 300 python bench.py --workload cfg3_aa_200x10k $pat --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $o/b.json 2> $o/b.err || tail -3 $o/b.err
+    PHYHIP_LIBDIR=phyml_amd/lib_diag PHYHIP_AA_NT=$nt timeout 300 python bench.py --full --workload cfg3_aa_200x10k $pat --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $o/b.json 2> $o/b.err || tail -3 $o/b.err
     python - "$nt" "$pat" <<'P'
 import json,sys
 d=json.load(open('bench_detail.json')); r=d['roofline']

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 o=gpurun_out/aa_var; mkdir -p $o
 for rep in 1 2 3; do
 for lib in lib "$@"; do
-    PHYHIP_LIBDIR=phyml_amd/$lib timeout 300 python bench.py --workload cfg3_aa_200x10k --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $o/b.json 2> $o/b.err || tail -3 $o/b.err
+    PHYHIP_LIBDIR=phyml_amd/$lib timeout 300 python bench.py --full --workload cfg3_aa_200x10k --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $o/b.json 2> $o/b.err || tail -3 $o/b.err
     python - "$lib" <<'P'
 import json,sys
 d=json.load(open('bench_detail.json')); r=d['roofline']
