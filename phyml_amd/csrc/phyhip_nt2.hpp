@@ -16,8 +16,8 @@
 // half the vector-memory instructions of an 8-byte form -- the per-CU vector-memory path is instruction-rate bound).
 // The host-facing layout ([pattern][category][state]) is restored by phyhip_get_partials.
 //
-// Everything else is the pipeline of traverse_nt_kernel: host-prepared buffer descriptors (size 0 = load
-// disabled, answered by the bounds check), loads of operation k+2 in flight while k is computed, results of
+// Everything else is the pipeline of traverse_nt_kernel: host-prepared buffer descriptors (size 0 = dead load: not
+// issued, the test is a scalar branch), loads of operation k+2 in flight while k is computed, results of
 // the last two operations forwarded in registers (two alternating register files, no copies), both
 // transition matrices of an operation staged once per wave into LDS and read back as broadcasts.
 #pragma once
@@ -121,23 +121,41 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
   };
   auto first_d = [](const u32x4 &v) { double d; __builtin_memcpy(&d, &v, 8); return d; };
 
-  // issue every load an operation needs (which ones are live was decided by the host)
+  // issue the loads an operation needs.  Which ones are live was decided by the host: a child that is a tip, forwarded in
+  // registers or computed in the step (in-step) has a data descriptor of size 0, a forwarded child a scale descriptor of size 0.
+  // Dead loads are not issued at all (the tests are on wave-uniform record words, so they are scalar branches): a 64-lane load
+  // through a size-0 descriptor still takes a vector-memory issue slot and its address processing, and on this path the
+  // per-CU vector-memory instruction rate is the limit.  Registers of a load not issued keep an older operation's value;
+  // the step reads them only for the children that were loaded.  List form only: a launch or command of one or two operations
+  // (ARGS) is a chain of dependent round trips, and the branches in front of its first loads made the large-grid SPR candidate
+  // slower (24.1 -> 25.4 us), so the short forms issue every load as before.
+  constexpr bool all = ARGS != 0;
   auto issue_data = [&](const IssueRec &o, Raw &r) {
     // one auxiliary dword per child: a tip child has no scale vector and an internal child no tip byte, so the host
     // points the same descriptor at whichever row exists (spare word x = 1: tip row, addressed by aligned dword)
-    const __amdgpu_buffer_rsrc_t d1r = rsrc(o.c1_data), d2r = rsrc(o.c2_data), g1r = rsrc(o.c1_scale), g2r = rsrc(o.c2_scale);
+    if (all || uni(o.c1_data.bytes))
+    {
+      const __amdgpu_buffer_rsrc_t d1r = rsrc(o.c1_data);
 #pragma unroll
-    for (int e = 0; e < HP; ++e) r.a[e] = __builtin_amdgcn_raw_buffer_load_b128(d1r, voff16, (unsigned)e * rowb, PHYHIP_LOAD_AUX);
+      for (int e = 0; e < HP; ++e) r.a[e] = __builtin_amdgcn_raw_buffer_load_b128(d1r, voff16, (unsigned)e * rowb, PHYHIP_LOAD_AUX);
+    }
+    if (all || uni(o.c2_data.bytes))
+    {
+      const __amdgpu_buffer_rsrc_t d2r = rsrc(o.c2_data);
 #pragma unroll
-    for (int e = 0; e < HP; ++e) r.b[e] = __builtin_amdgcn_raw_buffer_load_b128(d2r, voff16, (unsigned)e * rowb, PHYHIP_LOAD_AUX);
-    r.sa = __builtin_amdgcn_raw_buffer_load_b32(g1r, uni(o.c1_scale.x) ? (p & ~3u) : voff4, 0, 0);
-    r.sb = __builtin_amdgcn_raw_buffer_load_b32(g2r, uni(o.c2_scale.x) ? (p & ~3u) : voff4, 0, 0);
+      for (int e = 0; e < HP; ++e) r.b[e] = __builtin_amdgcn_raw_buffer_load_b128(d2r, voff16, (unsigned)e * rowb, PHYHIP_LOAD_AUX);
+    }
+    if (all || uni(o.c1_scale.bytes)) r.sa = __builtin_amdgcn_raw_buffer_load_b32(rsrc(o.c1_scale), uni(o.c1_scale.x) ? (p & ~3u) : voff4, 0, 0);
+    if (all || uni(o.c2_scale.bytes)) r.sb = __builtin_amdgcn_raw_buffer_load_b32(rsrc(o.c2_scale), uni(o.c2_scale.x) ? (p & ~3u) : voff4, 0, 0);
     if constexpr (INL)
-    { // the in-step child's second tip row (size 0 when the operation has no such child: the load is dropped)
+    { // the in-step child's second tip row (only an operation with such a child has one)
       const bool second = uni(o.c2_tip.x) != 0;
-      Desc       ct;
-      ct.base = second ? o.c2_tip.base : o.c1_tip.base; ct.bytes = second ? o.c2_tip.bytes : o.c1_tip.bytes; ct.x = 0;
-      r.tx = __builtin_amdgcn_raw_buffer_load_b32(rsrc(ct), p & ~3u, 0, 0);
+      if (second || uni(o.c1_tip.x) != 0)
+      {
+        Desc ct;
+        ct.base = second ? o.c2_tip.base : o.c1_tip.base; ct.bytes = second ? o.c2_tip.bytes : o.c1_tip.bytes; ct.x = 0;
+        r.tx = __builtin_amdgcn_raw_buffer_load_b32(rsrc(ct), p & ~3u, 0, 0);
+      }
     }
   };
   auto issue_pm = [&](const IssueRec &o, u32x4 &pc, u32x4 &pc2) {
@@ -147,11 +165,14 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
     const unsigned off = (mat ? uni(o.c2_data.x) : uni(o.c1_data.x)) + (unsigned)within * 16u;
     pc = __builtin_amdgcn_raw_buffer_load_b128(pm_rsrc, off, 0, 0);
     if constexpr (INL)
-    { // ... and of the in-step child's two matrices (matrix 0 when there is none: read, staged and never used)
-      const bool               c1 = uni(o.c1_tip.x) != 0, c2 = uni(o.c2_tip.x) != 0;
-      const unsigned long long ab = c2 ? o.c2_data.base : (c1 ? o.c1_data.base : 0ull);
-      const unsigned           off2 = (mat ? uni((unsigned)(ab >> 32)) : uni((unsigned)ab)) + (unsigned)within * 16u;
-      pc2 = __builtin_amdgcn_raw_buffer_load_b128(pm_rsrc, off2, 0, 0);
+    { // ... and of the in-step child's two matrices (only when there is such a child: otherwise staged from stale registers, never read)
+      const bool c1 = uni(o.c1_tip.x) != 0, c2 = uni(o.c2_tip.x) != 0;
+      if (c1 || c2)
+      {
+        const unsigned long long ab = c2 ? o.c2_data.base : o.c1_data.base;
+        const unsigned           off2 = (mat ? uni((unsigned)(ab >> 32)) : uni((unsigned)ab)) + (unsigned)within * 16u;
+        pc2 = __builtin_amdgcn_raw_buffer_load_b128(pm_rsrc, off2, 0, 0);
+      }
     }
   };
   auto issue = [&](const IssueRec &o, Raw &r, u32x4 &pc, u32x4 &pc2) {
@@ -223,6 +244,14 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
   const int last = ARGS ? 1 : q.n_ops - 1; // host pads the list to an even length
   Raw       RA, RB;
   u32x4     PA, PB, PA2, PB2; // (PA2 / PB2: INL only)
+  if constexpr (!all)
+  { // (loads that are skipped leave registers as they were: never undefined)
+    const u32x4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < HP; ++e) RA.a[e] = RA.b[e] = RB.a[e] = RB.b[e] = z;
+    RA.sa = RA.sb = RA.tx = RB.sa = RB.sb = RB.tx = 0u;
+    PA2 = PB2 = z;
+  }
   // The children of the first two operations do not depend on the matrices rebuilt below: their loads go out first and
   // travel while the prologue computes (a launch of one or two operations is a chain of dependent round trips --
   // kernel arguments, matrices, children, evaluation edge -- and every one taken off the chain is ~1 us of ~9).
@@ -324,6 +353,15 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
   {
     issue_pm(IR(0), PA, PA2);
     if constexpr (!single && DIST == 2) issue_pm(IR((1 < last) ? 1 : last), PB, PB2);
+    if constexpr (ARGS == 0)
+    { // The loop body sees [loads of k][stores of k-2][loads of k+1][stores of k-1] in flight when step k starts.  Two steps' worth of
+      // stores through a zero-sized descriptor (dropped by the hardware, but counted) give the loop entry the same shape: the
+      // compiler merges the counted waits of the entry and the loop's back edge, and without them the head of every even step
+      // waited for vmcnt(3) -- for the previous step's loads and stores too (as in traverse_aa_kernel).
+      const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(nullptr, 0, 0, 0x00020000);
+#pragma unroll
+      for (int i = 0; i < 2 * (HP + 1); ++i) __builtin_amdgcn_raw_buffer_store_b32(0u, none, 1024u * (unsigned)i, 0, 0); // (distinct offsets: identical stores would be merged)
+    }
     ExecRec  cur = XR(0);
     IssueRec nx2 = IR((DIST < last) ? DIST : last); // the next operation whose loads go out
 
