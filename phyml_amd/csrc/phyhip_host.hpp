@@ -1,7 +1,8 @@
 // phyhip_host.hpp -- what the translation units of libphyhip.so's host side share: the instance, the staging ring, the
 // instance table with the choke point of the resident protocol, and the declarations of each unit's functions.
 //   phyhip.hip           the C ABI: life cycle, inputs, transition matrices, the queueing entry points, getters, plumbing
-//   phyhip_queue.hip     the deferred queue turned into launches (flush_impl) and the waits for their scalars
+//   phyhip_queue.hip     the deferred queue turned into launches or resident commands (flush_impl and its stages),
+//                        the waits for their scalars
 //   phyhip_resident.hip  host side of the resident evaluators (small and large-grid)
 //   phyhip_eigen.hip     Update_Eigen_Lr / dLk entry points
 //   phyhip_mixture.hip   mixtures (class instances, class axis)
@@ -541,14 +542,12 @@ struct EdgeEval
 int  flush_uploads(Instance *I);
 int  flush_pmats(Instance *I);
 bool fuse_reduce(const Instance *I, int nblocks);
-int  flush_impl(Instance *I, const EdgeEval *ee);
 int  flush(Instance *I, const EdgeEval *ee);
 int  flush_sync(Instance *I);
 int  flush_and_wait(Instance *I, EdgeEval &ee, bool flushed = false);
 int  check_partial_index(const Instance *I, int idx, bool allow_tip);
 int  wait_host_sum(Instance *I);
 int  wait_result(Instance *I);
-int  wait_result_impl(Instance *I);
 int  collect_profile(Instance *I);
 void devirtualise(Instance *I, int buf);       // queue (in front) the storing operation that makes buffer `buf` real again
 void devirtualise_all(Instance *I);
