@@ -9,9 +9,9 @@
 // constants and table read out of its .rodata (they are the published ones of ARM's optimized-routines;
 // tests/test_exp_port.py::test_the_table_is_the_one_in_libm finds them in the image's libm.so.6) -- the subnormal-result and
 // out-of-range branches included.  Pinned on the CPU against libm itself: tests/test_exp_port.py (this header compiled by gcc,
-// 4 x 10^7 inputs per run, 2 x 10^8 when it was written: 0 differ); on the device through what it produces: transition matrices
-// equal to the reference's own dumps and to the restatement's over the whole range of edge lengths, bit for bit
-// (tests/test_gpu_parity.py::test_device_pmatrices, tests/test_gpu_cases.py::test_device_built_matrices_at_every_category_count).
+// 4 x 10^7 inputs per run, 2 x 10^8 when it was written: 0 differ); on the device through what it produces: the matrices of every
+// builder -- pmat_kernel / pmat20_kernel and the rebuilds folded into the evaluation kernels, rare branches included -- equal to
+// the restatement's bit for bit (tests/test_gpu_folded_matrices.py; the standalone kernels also in tests/test_gpu_cases.py).
 // -ffp-contract=off (the build's flag) keeps the unfused operations unfused.
 #pragma once
 #include <stdint.h>

@@ -22,10 +22,8 @@ def device_tree_from_golden(d, host_pmat=True, devices=None, force_sharded=False
     return t, ot
 
 
-def synthetic_pair(n_otu, P, ns, C, seed, lmin=0.02, lmax=0.3, wght=None, apply_scaling=1, host_pmat=True, ambiguous_every=0,
-                   devices=None, force_sharded=False, use_m4mod=False, arith=1):
-    """Device tree + oracle tree on a seeded synthetic alignment with C rate classes (rates/weights made up,
-    normalised) and the committed model block's eigen system."""
+def synthetic_oracle(n_otu, P, ns, C, seed, lmin=0.02, lmax=0.3, wght=None, apply_scaling=1, ambiguous_every=0, arith=1):
+    """The oracle half of synthetic_pair (no device needed): (oracle tree, random tree, states, tip vectors, weights)."""
     from phyml_amd import synth, workloads
     blk = dict(workloads.model_block("model_gtr_g4" if ns == 4 else "model_lg_g4"))
     rates = np.linspace(0.2, 2.2, C) if C > 1 else np.array([1.0])
@@ -47,9 +45,31 @@ def synthetic_pair(n_otu, P, ns, C, seed, lmin=0.02, lmax=0.3, wght=None, apply_
         v, s, a = orc.init_tip(m.datatype, chars[t])
         tv.append(v); ds.append(s); amb_.append(a)
     ot = orc.OracleTree(m, n_otu, tree.edge_left, tree.edge_rght, tree.edge_len, wg, tv, ds, amb_, apply_scaling=apply_scaling, arith=arith)
+    return ot, tree, st, tv, wg
+
+
+def synthetic_pair(n_otu, P, ns, C, seed, lmin=0.02, lmax=0.3, wght=None, apply_scaling=1, host_pmat=True, ambiguous_every=0,
+                   devices=None, force_sharded=False, use_m4mod=False, arith=1):
+    """Device tree + oracle tree on a seeded synthetic alignment with C rate classes (rates/weights made up,
+    normalised) and the committed model block's eigen system."""
+    ot, tree, st, tv, wg = synthetic_oracle(n_otu, P, ns, C, seed, lmin, lmax, wght, apply_scaling, ambiguous_every, arith)
+    m = ot.m
     t = lktree.LkTree(n_otu, tree.edge_left, tree.edge_rght, tree.edge_len, P, ns, C, host_pmat=host_pmat, devices=devices,
                       force_sharded=force_sharded, use_m4mod=use_m4mod)
     t.set_model(m.pi, m.gamma_rr, m.gamma_r_proba, m.e_val, m.r_e_vect, m.l_e_vect, m.l_min, m.l_max, 1.0, apply_scaling)
     t.Make_Tree_For_Lk(wg)
     t.set_tips(tip_partials=tv)
     return t, ot, tree, st
+
+def assert_device_state_is_the_oracles(t, ot, buffer_of=None, what=None):
+    """What a call sequence left in device memory against the oracle tree that followed it: every transition matrix of the tree
+    and every partial vector and scale vector of the tree's own buffers, bit for bit (patterns of weight zero excepted, as
+    everywhere: the reference skips them).  buffer_of: {(edge, side): device buffer index} where the caller addressed the buffers
+    itself (a replayed stream); else the host layer's own indices."""
+    for e in range(ot.ne):
+        assert np.array_equal(t.inst.get_transition_matrix(e), ot.pm[e]), (what, "matrix", e)
+    w = ot.wght > 0
+    for (e, side), p in ot.plk.items():
+        idx = t.side_buffer(e, side) if buffer_of is None else buffer_of[(e, side)]
+        assert np.array_equal(t.inst.get_partials(idx)[w], p[w]), (what, "partials", e, side)
+        assert np.array_equal(t.inst.get_scale_factors(idx)[w], ot.scale[(e, side)][w]), (what, "scale", e, side)

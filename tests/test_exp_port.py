@@ -1,8 +1,8 @@
 """phyml_amd/csrc/phyhip_exp.hpp -- the device's exp() -- compiled by gcc for the host and held against this image's libm, the
 one the reference calls (src/models.c:275, src/lk.c:712-713): the same double for every input tried, the branches for
 subnormal results, out-of-range arguments, infinities and NaNs included.  (The device runs the same header: its FMA and its
-plain multiply / add are IEEE operations like the host's; tests/test_gpu_cases.py::test_device_built_matrices_at_every_category_count
-and tests/test_gpu_parity.py::test_device_pmatrices hold what it produces to the reference's matrices bit for bit.)"""
+plain multiply / add are IEEE operations like the host's; tests/test_gpu_folded_matrices.py holds what every matrix builder
+makes of it to the restatement's matrices bit for bit, the rare branches included.)"""
 import os
 import subprocess
 

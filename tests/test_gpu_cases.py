@@ -73,8 +73,10 @@ def test_device_built_matrices_at_every_category_count(ns, C):
             ot.len[e] = l
             ot.update_pmat(e)
             assert np.array_equal(t.inst.get_transition_matrix(e), ot.pm[e]), e
-        # lengths over the whole range the clamp lets through (l_min ... l_max x rate: exp() of arguments down to the subnormal
-        # results' branch), zero and negative lengths (src/lk.c:2296: MAX(0, l)), one matrix at a time and all at once
+        # lengths over the whole range the clamp lets through (l_min ... l_max after the rate: with the committed eigen systems
+        # exp()'s arguments run from -176 (4 states) / -212 (20 states) up to the near-zero first eigenvalue's |x| < 2^-54 -- the
+        # 1 + x branch; the branches from |x| = 512 on are NOT reached here: tests/test_gpu_folded_matrices.py opens the clamps
+        # for them), zero and negative lengths (src/lk.c:2296: MAX(0, l)), one matrix at a time and all at once
         rng = np.random.default_rng(11 * ns + C)
         lens = np.concatenate([10.0 ** rng.uniform(-9, 2.3, 3 * ot.ne - 3), [0.0, -0.25, 1e-300]])
         for k in range(0, len(lens), ot.ne):

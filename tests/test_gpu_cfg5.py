@@ -145,7 +145,7 @@ def test_recorded_200_taxon_search_at_100k_patterns():
         w = np.zeros(len(k), bool); w[lo:hi] = True
         sc = w & np.isin(k, (replay.EDGE_LNL, replay.DLK))
         assert sc.sum() > 1000
-        assert np.max(np.abs(got[sc] - ref[sc]) / np.abs(ref[sc])) < 1e-9   # (device-built matrices: device exp)
+        assert np.max(np.abs(got[sc] - ref[sc]) / np.abs(ref[sc])) < 1e-10  # (the references are chunk sums, as above; device-built matrices are the oracle's doubles)
         dl = w & (k == replay.DLK)
         if dl.any():
             assert np.max(np.abs(got2[dl] - ref2[dl]) / np.maximum(1.0, np.abs(ref2[dl]))) < 1e-6

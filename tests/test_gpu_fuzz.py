@@ -38,17 +38,16 @@ def test_random_configuration(ns, i):
         t.Set_Both_Sides(1 if c["both"] else 0)
         lnl = t.Lk(None)
         ref = ot.lk(None, both_sides=c["both"])
-        tol = 1e-12 if c["host_pmat"] else 1e-9
+        tol = 1e-12  # (both matrix routes: device-built matrices are the oracle's doubles, phyml_amd/csrc/phyhip_exp.hpp)
         assert abs(lnl - ref) <= tol * abs(ref), (c, lnl, ref)
         w = ot.wght > 0
-        if c["host_pmat"]:
-            for (e, side), p in ot.plk.items():
-                if not c["both"] and not np.any(p):
-                    continue
-                assert np.array_equal(t.partials(e, side)[w], p[w]), (c, e, side)
-                assert np.array_equal(t.scale_factors(e, side)[w], ot.scale[(e, side)][w]), (c, e, side)
+        for (e, side), p in ot.plk.items():
+            if not c["both"] and not np.any(p):
+                continue
+            assert np.array_equal(t.partials(e, side)[w], p[w]), (c, e, side)
+            assert np.array_equal(t.scale_factors(e, side)[w], ot.scale[(e, side)][w]), (c, e, side)
         site = t.inst.site_outputs()[0]
-        assert np.max(np.abs(site[w] - ot.c_lnL_sorted[w])) < (1e-10 if c["host_pmat"] else 1e-7)
+        assert np.max(np.abs(site[w] - ot.c_lnL_sorted[w])) < 1e-10
         if c["both"]:
             ne = 2 * c["n"] - 3
             for e in {int(x) % ne for x in synth.hash_u64(7, i, np.arange(3))}:
@@ -62,6 +61,6 @@ def test_random_configuration(ns, i):
                 lv, la = t.dLk(l, e)
                 da = t.c_dlnL
                 _, lb, db = ot.dlk(l)
-                assert abs(la - lb) <= tol * abs(lb) and abs(da - db) <= 1e-7 * max(1.0, abs(db)), (c, e, l, la, lb, da, db)
+                assert abs(la - lb) <= tol * abs(lb) and abs(da - db) <= 1e-8 * max(1.0, abs(db)), (c, e, l, la, lb, da, db)
     finally:
         t.close()

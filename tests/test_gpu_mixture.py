@@ -61,7 +61,7 @@ def test_lg4x_mixture_on_device(host_pmat, layout, fx):
         ref = float(d["lnL"][0])
         assert abs(lnl - ref) <= (1e-13 if host_pmat else 1e-11) * abs(ref), (lnl, ref)
         logs = trees[0].inst.site_log_likelihoods()
-        assert np.max(np.abs(logs - d["c_lnL_sorted"])) < (1e-11 if host_pmat else 1e-9)
+        assert np.max(np.abs(logs - d["c_lnL_sorted"])) < 1e-11  # (either matrix route: device-built matrices are the reference's doubles)
         for k, t in enumerate(trees):  # per-class pieces the combination used
             _, _, u, f = t.inst.site_outputs()
             assert np.array_equal(np.asarray(f), d[f"class{k}_fact"])
@@ -164,7 +164,7 @@ def test_lg4x_mixture_on_the_class_axis(host_matrices, layout, fx):
         ref = float(d["lnL"][0])
         assert abs(lnl - ref) <= (1e-13 if host_matrices else 1e-11) * abs(ref), (lnl, ref)
         logs = t.inst.site_log_likelihoods()
-        assert np.max(np.abs(logs - d["c_lnL_sorted"])) < (1e-11 if host_matrices else 1e-9)
+        assert np.max(np.abs(logs - d["c_lnL_sorted"])) < 1e-11  # (either matrix route)
         _, _, u, f = t.inst.site_outputs(n_fact=K)
         u = np.asarray(u).reshape(-1, K); f = np.asarray(f).reshape(K, -1)
         for k in range(K):

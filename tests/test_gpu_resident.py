@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import orc  # noqa: F401
-from gpu_common import device_tree_from_golden, synthetic_pair
+from gpu_common import assert_device_state_is_the_oracles, device_tree_from_golden, synthetic_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -134,7 +134,8 @@ def test_two_instances_each_with_resident_workgroups():
 def test_resident_short_evaluations_spr_call_pattern(taxa, patterns, categories, monkeypatch):
     """A seeded SPR / Br_Len_Opt call stream (phyml_amd/replay.py: matrix refreshes, partial updates, edge likelihoods, eigen
     products, dLk chains) with both resident evaluators against a kernel launch per call: the same doubles, scalar by
-    scalar, and the oracle's values; device-built matrices (the resident workgroups rebuild them in their prologue)."""
+    scalar, and the oracle's values; device-built matrices (the resident workgroups rebuild them in their prologue), which are
+    the oracle's doubles -- and so is everything the stream leaves in device memory."""
     from phyml_amd import replay
     import replay_oracle
     res, stats = {}, {}
@@ -149,9 +150,12 @@ def test_resident_short_evaluations_spr_call_pattern(taxa, patterns, categories,
             stats[r] = (t.inst.resident_stats(0), t.inst.resident_stats(1))
             if r == "1":
                 ot.lk(None, both_sides=True)
-                ref, ref2 = replay_oracle.OracleReplayer(ot).run(tr)
+                rep = replay_oracle.OracleReplayer(ot)
+                ref, ref2 = rep.run(tr)
                 m = ref != 0
-                assert np.max(np.abs(res[r][0][m] - ref[m]) / np.abs(ref[m])) < 1e-9  # (device exp in the matrices)
+                assert np.max(np.abs(res[r][0][m] - ref[m]) / np.abs(ref[m])) < 1e-12
+                # ... and what the stream left behind: the oracle's matrices, partial vectors and scale vectors, bit for bit
+                assert_device_state_is_the_oracles(t, ot, {key: idx for idx, key in rep.key_of.items()}, (taxa, patterns, categories))
         finally:
             t.close()
     assert np.array_equal(res["0"][0], res["1"][0]) and np.array_equal(res["0"][1], res["1"][1])
@@ -258,12 +262,20 @@ def test_large_grid_resident_evaluator_spr_and_brlen_call_pattern(taxa, patterns
             assert t.inst.numerical_warning() == 0
             if r == "1":
                 full = ot.lk(None, both_sides=True)
-                ref, ref2 = replay_oracle.OracleReplayer(ot).run(tr)
+                rep = replay_oracle.OracleReplayer(ot)
+                ref, ref2 = rep.run(tr)
                 m = ref != 0
-                assert np.max(np.abs(res[r][0][m] - ref[m]) / np.abs(ref[m])) < 1e-9  # (device exp in the matrices)
+                assert np.max(np.abs(res[r][0][m] - ref[m]) / np.abs(ref[m])) < 1e-12
                 dl = tr["kind"] == replay.DLK
                 assert np.max(np.abs(res[r][1][dl] - ref2[dl]) / np.maximum(1.0, np.abs(ref2[dl]))) < 1e-7
                 assert abs(again - full) / abs(full) < 1e-11
+                if patterns <= 9000:
+                    # what the stream leaves behind (the smaller shapes: the read-backs stay cheap).  The traversal above has put
+                    # the tree's own matrices and buffers back, so the stream runs once more -- the same scalars -- and its state
+                    # is read where the oracle's replay stands: matrices, partial vectors, scale vectors, bit for bit
+                    once_more = t.Replay_Surface_Trace(tr)
+                    assert np.array_equal(once_more[0], res[r][0]) and np.array_equal(once_more[1], res[r][1])
+                    assert_device_state_is_the_oracles(t, ot, {key: idx for idx, key in rep.key_of.items()}, (taxa, patterns, categories))
         finally:
             t.close()
     assert np.array_equal(res["0"][0], res["1"][0]) and np.array_equal(res["0"][1], res["1"][1]) and res["0"][2] == res["1"][2]
@@ -345,8 +357,10 @@ def test_two_large_instances_share_one_device(monkeypatch):
                 got, got2 = t.Replay_Surface_Trace(tr)
                 ref, ref2 = replay_oracle.OracleReplayer(ot).run(tr)
                 m = ref != 0
-                assert np.max(np.abs(got[m] - ref[m]) / np.abs(ref[m])) < 1e-9
+                assert np.max(np.abs(got[m] - ref[m]) / np.abs(ref[m])) < 1e-12
         assert sum(t.inst.resident_stats(2)[0] for t, *_ in pairs) > 0
+        for t, ot, tree, st in pairs:  # what the streams left behind: the oracle's matrices and vectors, bit for bit
+            assert_device_state_is_the_oracles(t, ot, {key: idx for idx, key in replay_oracle.OracleReplayer(ot).key_of.items()}, ot.P)
     finally:
         for t, *_ in pairs:
             t.close()
@@ -387,11 +401,21 @@ def test_20_state_resident_evaluator_is_the_launch_path_bit_for_bit(P, C, host_p
             # what is left in device memory: matrices (both tables feed later launches) and the buffers the stream wrote
             mats = [t.inst.get_transition_matrix(e).copy() for e in range(ot.ne)]
             bufs = [t.partials(e, s).copy() for e in (0, 5, 11, ot.ne - 1) for s in (0, 1) if (e, s) in ot.plk]
+            rep = OracleReplayer(ot)
+            left = None
+            if res == "1" and not host_pmat:  # (every buffer of the tree as the stream left it, for the oracle's replay below)
+                left = {key: (t.inst.get_partials(idx).copy(), t.inst.get_scale_factors(idx).copy()) for idx, key in rep.key_of.items()}
             after = t.Lk(None)   # a launched list-form traversal on whatever the residents left in the A-operand table
             if res == "1":
-                oref, oref2 = OracleReplayer(ot).run(tr)
+                oref, oref2 = rep.run(tr)
                 lnl_calls = (k == replay.EDGE_LNL) | (k == replay.DLK)
                 assert np.max(np.abs(got[lnl_calls] - oref[lnl_calls]) / np.abs(oref[lnl_calls])) < 1e-11
+                if not host_pmat:
+                    # device-built matrices are the oracle's doubles: so is everything the stream left behind, bit for bit
+                    for e in range(ot.ne):
+                        assert np.array_equal(mats[e], ot.pm[e]), e
+                    for key, (p, sc) in left.items():
+                        assert np.array_equal(p, ot.plk[key]) and np.array_equal(sc, ot.scale[key]), key
             vals[res] = (got, got2, mats, bufs, after, ref0)
         finally:
             t.close()
