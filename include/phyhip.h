@@ -216,6 +216,29 @@ int phyhip_get_site_log_likelihoods(int instance, double *outLogLikelihoods);
 int phyhip_get_site_outputs(int instance, double *c_lnL_sorted, double *cur_site_lk,
                             double *unscaled_site_lk_cat, int *fact_sum_scale);
 
+/* The per-pattern outputs of Lk_Core at one edge as the REFERENCE's doubles, bit for bit -- what host readers that compare or
+   rank them need (aLRT / SH-like supports, --print_site_lnl, cv.c, ancestral reconstruction).  phyhip_get_site_outputs returns
+   what the last evaluation of the hot path left: equal to the reference to 1e-10 / 1e-12 only (the evaluation kernels take the
+   general product for every pattern and the device library's log).  This call evaluates the edge again in a kernel of its own,
+   operation by operation as Lk_Core does (src/lk.c:767-861, src/avx.c:110-215, Pull_Scaling_Factors): the tip branch
+   pi[s] * norm(P[s][.] o left) where the child is a tip with exactly one allowed state, the general product elsewhere, the +I
+   mixing with Invariant_Lk's overflow branch, the SMALL floor (-> *outNumericalWarning = 1), glibc's log and exp.
+     parent = left side, child = right side; either may be a tip index.  Precondition as in the reference: the partials on both
+   sides are current (queued operations are executed first, virtual buffers stored).  Any output pointer may be NULL.
+     c_lnL_sorted, cur_site_lk [pattern]; unscaled_site_lk_cat [pattern][category]; fact_sum_scale [pattern].  Entries of
+   patterns whose weight is not above SMALL are written as 0 (the reference leaves them stale).
+     *outSumLogLikelihood: the sum over the patterns in ascending order of the rounded products weight x c_lnL_sorted (src/lk.c:856),
+   formed on the host -- for a sharded instance over all its patterns, so sharding does not change it.
+     Nothing else changes: the outputs of the last evaluation (phyhip_get_site_outputs, phyhip_get_site_log_likelihoods), the
+   numerical warning, every partial, scale vector and matrix stay what they were.
+     One-process-per-GPU form (phyhip_comm_init_rank): the call is LOCAL to the rank -- its own patterns, its own sum, no collective.
+     Instances created with PHYHIP_FLAG_CLASS_AXIS or PHYHIP_FLAG_GENERIC_LOOP: PHYHIP_ERROR_NO_IMPLEMENTATION.  1 .. 64 categories. */
+int phyhip_calculate_edge_site_outputs_exact(int instance, int parentBufferIndex, int childBufferIndex,
+                                             int probabilityIndex,
+                                             double *c_lnL_sorted, double *cur_site_lk,
+                                             double *unscaled_site_lk_cat, int *fact_sum_scale,
+                                             double *outSumLogLikelihood, int *outNumericalWarning);
+
 /* replaces beagleGetPartials, src/beagle_utils.c:252 (download hook for ancestral.c, cv.c, m4.c ...) */
 int phyhip_get_partials(int instance, int bufferIndex, int scaleIndex, double *outPartials);
 

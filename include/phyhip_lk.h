@@ -171,6 +171,12 @@ void Replay_Surface_Trace(t_tree *tree, int n_rec, const int *kind, const int *a
 /* download hooks for host readers (ancestral.c, cv.c, io.c) */
 void Get_Partial_Lk(t_tree *tree, t_edge *b, t_node *d, phydbl *p_lk, int *sum_scale);
 void Get_Site_Lk(t_tree *tree, phydbl *c_lnL_sorted, phydbl *cur_site_lk, phydbl *unscaled_site_lk_cat, int *fact_sum_scale);
+/* The same arrays for edge b as the reference's doubles, bit for bit (phyhip_calculate_edge_site_outputs_exact): what aLRT,
+   --print_site_lnl and cv.c read.  b == NULL: the edge Lk(NULL) evaluates (e_root, else a_nodes[tip_root]->b[0]) -- no traversal:
+   as in the reference the partials on both sides of b must be current.  Returns the ordered sum of weight x c_lnL_sorted;
+   tree->c_lnL and the outputs Get_Site_Lk returns are left alone.  Any pointer may be NULL. */
+phydbl Get_Exact_Site_Lk(t_tree *tree, t_edge *b, phydbl *c_lnL_sorted, phydbl *cur_site_lk, phydbl *unscaled_site_lk_cat,
+                         int *fact_sum_scale);
 
 void Set_Exit_Handler(void (*handler)(const char *msg));
 

@@ -47,6 +47,7 @@ SYMBOLS = [
     "phyhip_calculate_mixture_eigen_lnl_dlnl", "phyhip_comm_get_unique_id", "phyhip_comm_init_rank", "phyhip_comm_size",
     "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_calculate_class_mixture_log_likelihood",
     "phyhip_calculate_class_mixture_eigen_lnl_dlnl", "phyhip_get_class_scale_factors", "phyhip_set_mixture_invariant_sites",
+    "phyhip_calculate_edge_site_outputs_exact",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -229,6 +230,15 @@ class Instance:
         a = np.zeros(self.P); b = np.zeros(self.P); c = np.zeros((self.P, self.C)); f = np.zeros(self.P * n_fact, np.int32)
         _chk(self.L.phyhip_get_site_outputs(self.id, _ptr(a), _ptr(b), _ptr(c), _ptr(f)))
         return a, b, c, f
+
+    def exact_site_outputs(self, parent, child, pmat):
+        """phyhip_calculate_edge_site_outputs_exact: (c_lnL_sorted, cur_site_lk, unscaled_site_lk_cat, fact_sum_scale, ordered
+        sum, numerical warning) of the edge as the reference's doubles; nothing the last evaluation left is touched."""
+        a = np.zeros(self.P); b = np.zeros(self.P); c = np.zeros((self.P, self.C)); f = np.zeros(self.P, np.int32)
+        s = C.c_double(0.0); w = C.c_int(0)
+        _chk(self.L.phyhip_calculate_edge_site_outputs_exact(self.id, int(parent), int(child), int(pmat), _ptr(a), _ptr(b), _ptr(c),
+                                                             _ptr(f), C.byref(s), C.byref(w)))
+        return a, b, c, f, s.value, w.value
 
     def get_partials(self, buf):
         out = np.zeros((self.P, self.C * self.S))

@@ -751,3 +751,15 @@ void Get_Site_Lk(t_tree *tree, phydbl *c_lnL_sorted, phydbl *cur_site_lk, phydbl
 {
   CHK(phyhip_get_site_outputs(tree->b_inst, c_lnL_sorted, cur_site_lk, unscaled_site_lk_cat, fact_sum_scale));
 }
+
+phydbl Get_Exact_Site_Lk(t_tree *tree, t_edge *b, phydbl *c_lnL_sorted, phydbl *cur_site_lk, phydbl *unscaled_site_lk_cat,
+                         int *fact_sum_scale)
+{
+  double lnl = 0.0;
+  if (b == NULL) b = tree->e_root ? tree->e_root : tree->a_nodes[tree->tip_root]->b[0]; /* src/lk.c:573-579 */
+  const int left = b->left->tax ? b->left->num : b->p_lk_left_idx;
+  const int rght = b->rght->tax ? b->p_lk_tip_idx : b->p_lk_rght_idx;
+  CHKV(phyhip_calculate_edge_site_outputs_exact(tree->b_inst, left, rght, b->Pij_rr_idx, c_lnL_sorted, cur_site_lk,
+                                                unscaled_site_lk_cat, fact_sum_scale, &lnl, NULL), 0.0);
+  return lnl;
+}

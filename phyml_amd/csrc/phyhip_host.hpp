@@ -8,6 +8,7 @@
 //   phyhip_mixture.hip   mixtures (class instances, class axis)
 //   phyhip_shard.hip     pattern shards over several devices, the one collective
 //   phyhip_big.hip       instantiations of resident_big_kernel (its own compile flags)
+//   phyhip_exact.hip     the per-pattern outputs of an edge as the reference's doubles (a kernel and an entry point of its own)
 // Internal: nothing here is part of the ABI (include/phyhip.h).
 #pragma once
 #include "../../include/phyhip.h"
@@ -204,6 +205,7 @@ struct Instance
   double   *d_pi, *d_catw, *d_catr, *d_eval, *d_evec, *d_ivec;
   double   *d_site_lnl = nullptr, *d_site_lk = nullptr, *d_site_cat = nullptr, *d_dot = nullptr;
   int      *d_fact     = nullptr;
+  void     *d_exact    = nullptr; // outputs of phyhip_calculate_edge_site_outputs_exact (phyhip_exact.hip), allocated on first use
   double   *d_block    = nullptr; // [2][grid]
   double   *d_result   = nullptr; // [2]
   double   *h_result   = nullptr; // pinned, device-visible: [0..1] results, [2] sequence number (as u64)

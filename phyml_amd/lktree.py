@@ -71,7 +71,7 @@ def load():
         L = C.CDLL(LK_LIB_PATH)
         L.Make_Tree_From_Edges.restype = C.POINTER(t_tree)
         L.Make_Model_Basic.restype = C.POINTER(t_mod)
-        for f in ("Lk", "dLk", "Br_Len_Newton", "Update_Lk_At_Given_Edge"):
+        for f in ("Lk", "dLk", "Br_Len_Newton", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk"):
             getattr(L, f).restype = C.c_double
         # tests must survive the reference's print-and-Exit() convention
         L.Set_Exit_Handler(_exit_handler)
@@ -199,6 +199,15 @@ class LkTree:
         v = self.L.Lk(None if b is None else self.edge(b), self.tree)
         _raise_if_error()
         return v
+
+    def Exact_Site_Lk(self, b=None):
+        """Get_Exact_Site_Lk: (ordered sum, c_lnL_sorted, cur_site_lk, unscaled_site_lk_cat, fact_sum_scale) of edge b (None: the
+        edge Lk(None) evaluates) as the reference's doubles; the partials on both sides of b must be current."""
+        a = np.zeros(self.P); c = np.zeros(self.P); u = np.zeros((self.P, self.C)); f = np.zeros(self.P, np.int32)
+        v = self.L.Get_Exact_Site_Lk(self.tree, None if b is None else self.edge(b), _dp(a), _dp(c), _dp(u),
+                                     f.ctypes.data_as(C.c_void_p))
+        _raise_if_error()
+        return v, a, c, u, f
 
     def dLk(self, l, b):
         lv = C.c_double(l)
