@@ -120,6 +120,31 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(base), 0, (int)uni(d.bytes), 0x00020000);
   };
   auto first_d = [](const u32x4 &v) { double d; __builtin_memcpy(&d, &v, 8); return d; };
+  // maximum of a 32-bit value over the G lanes of a pattern (lanes pl, pl + PW, ...): the half-exchange instructions of gfx950
+  // put both partners' values side by side in registers -- no LDS round trip on the step's chain (as phyhip_aa.hpp's xor16_pair /
+  // xor32_pair).  An integer maximum: the same bits as the shuffle it replaces.
+  // List form only: the short forms keep the shuffle (their call times were not re-measured with the exchange, and small changes
+  // to them have cost the large-grid SPR candidate before: profiles/r07_nt_step.md).
+  auto group_max = [](unsigned v) {
+    static_assert(G == 1 || G == 2 || G == 4, "lanes of a pattern: 32 or 16 apart");
+    if constexpr (ARGS != 0)
+    {
+#pragma unroll
+      for (int d = PW; d < 64; d <<= 1) v = max(v, (unsigned)__shfl_xor((int)v, d, 64));
+      return v;
+    }
+    if constexpr (G == 4)
+    {
+      const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+      v = max((unsigned)r[0], (unsigned)r[1]);
+    }
+    if constexpr (G >= 2)
+    {
+      const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+      v = max((unsigned)r[0], (unsigned)r[1]);
+    }
+    return v;
+  };
 
   // issue the loads an operation needs.  Which ones are live was decided by the host: a child that is a tip, forwarded in
   // registers or computed in the step (in-step) has a data descriptor of size 0, a forwarded child a scale descriptor of size 0.
@@ -231,6 +256,23 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
         }
     }
   };
+
+  // an operation's matrix piece(s) from the registers they were loaded into to LDS buffer `parity`
+  auto stage_pm = [&](const int parity, const u32x4 &pc, const u32x4 &pc2) {
+    double2 *b = reinterpret_cast<double2 *>(&lds_p[parity][0]);
+    double2  v;
+    __builtin_memcpy(&v, &pc, 16);
+    b[(lane < 16 * C) ? lane : 0] = v;
+    if constexpr (INL)
+    {
+      __builtin_memcpy(&v, &pc2, 16);
+      b[16 * C + ((lane < 16 * C) ? lane : 0)] = v;
+    }
+  };
+  // List form, loads two operations ahead: a step's scalar record loads and the LDS write of the NEXT operation's matrices sit in
+  // the step's second half, which reads nothing from LDS (see step).  The short forms keep their order: changes in front of their
+  // first loads cost the large-grid SPR candidate (profiles/r07_nt_step.md).
+  constexpr bool early = !all && DIST == 2;
 
   // records: device slot ring, or the kernel arguments for launches of one or two operations (last <= 1)
   auto IR = [&](int i) -> IssueRec {
@@ -353,6 +395,7 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
   {
     issue_pm(IR(0), PA, PA2);
     if constexpr (!single && DIST == 2) issue_pm(IR((1 < last) ? 1 : last), PB, PB2);
+    if constexpr (early) stage_pm(0, PA, PA2); // (step k stages the matrices of k+1: the first step's are staged here)
     if constexpr (ARGS == 0)
     { // The loop body sees [loads of k][stores of k-2][loads of k+1][stores of k-1] in flight when step k starts.  Two steps' worth of
       // stores through a zero-sized descriptor (dropped by the hardware, but counted) give the loop entry the same shape: the
@@ -367,22 +410,24 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
 
     // One pipeline step: operation k; its loads are in (R, PC); Fprev = result of k-1, Fout = result of k-2
     // on entry and the result of k on exit.
-    auto step = [&](const int k, const int parity, Raw &R, u32x4 &PC, u32x4 &PC2, double (&Fout)[CS], unsigned &scout,
-                    const double (&Fprev)[CS], const unsigned scprev) {
+    // (PN, PN2: the matrix piece(s) of operation k+1, loaded by step k-1)
+    auto step = [&](const int k, const int parity, Raw &R, u32x4 &PC, u32x4 &PC2, const u32x4 &PN, const u32x4 &PN2,
+                    double (&Fout)[CS], unsigned &scout, const double (&Fprev)[CS], const unsigned scprev) {
       PHY_STAMP(k, 0)
-      // the execute record of operation k+1 is the first thing the next step needs (its flags steer the operand
-      // selection): its scalar load goes out first so that it has the whole step to come back from L2
-      const ExecRec nx1 = XR((k + 1 < last) ? k + 1 : last);
+      ExecRec  nx1;
       double2 *buf = reinterpret_cast<double2 *>(&lds_p[parity][0]);
-      {
-        double2 v;
-        __builtin_memcpy(&v, &PC, 16);
-        buf[(lane < 16 * C) ? lane : 0] = v;
-        if constexpr (INL)
-        {
-          __builtin_memcpy(&v, &PC2, 16);
-          buf[16 * C + ((lane < 16 * C) ? lane : 0)] = v;
-        }
+      if constexpr (!early)
+      { // the execute record of operation k+1 is the first thing the next step needs (its flags steer the operand
+        // selection): its scalar load goes out first so that it has the whole step to come back from L2
+        nx1 = XR((k + 1 < last) ? k + 1 : last);
+        stage_pm(parity, PC, PC2);
+      }
+      else
+      { // Both records the previous step asked for (cur, nx2) are waited for HERE, before the first LDS read: scalar loads and
+        // LDS share a counter and scalar loads return out of order, so one still in flight turns every counted wait for a
+        // batch of matrix reads into a drain.  The matrices were staged by the previous step.
+        asm volatile("" ::"s"(uni(nx2.c1_scale.bytes)), "s"(uni(cur.dst_scale.bytes)));
+        __builtin_amdgcn_sched_barrier(0);
       }
       __builtin_amdgcn_wave_barrier();
       const double *bufd = &lds_p[parity][0];
@@ -414,11 +459,7 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
           }
           if constexpr (G > 1)
           {
-            if (!cls)
-            {
-#pragma unroll
-              for (int d = PW; d < 64; d <<= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, d, 64));
-            }
+            if (!cls) mx = group_max(mx);
           }
           if (mx < kHiInvTwoToLarge && q.apply_scaling)
           {
@@ -505,10 +546,25 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       }
 
       PHY_STAMP(k, 3)
+      IssueRec nx3;
+      if constexpr (early)
+      { // The last LDS result of the step has been consumed; from here to the stores the step issues no LDS read.  The scalar
+        // records of the next step go out now and are first used at its head, a product, a rescaling and the stores later; and
+        // the next operation's matrices (in registers since step k-1 asked for them) go into the LDS buffer step k-1 read from.
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0): the compiler would wait for the last matrix reads at the product, with the scalar loads in flight
+        nx1 = XR((k + 1 < last) ? k + 1 : last);
+        stage_pm(parity ^ 1, PN, PN2);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       // prefetch operation k+2 into the registers just freed; then the scalar records of the next step
       if constexpr (!ARGS) issue(nx2, R, PC, PC2); // (records in the arguments: at most two operations, nothing to prefetch)
       PHY_STAMP(k, 7)
-      const IssueRec nx3 = IR((k + 1 + DIST < last) ? k + 1 + DIST : last);
+      // (the issue record only now: it takes over the scalar registers of the one the prefetch has just consumed.  With in-step
+      // children -- 24 words instead of 16 -- the register allocator still re-loads it at the next step's head, where the
+      // parent's loop had it too: profiles/r09_nt_chain.md)
+      nx3 = IR((k + 1 + DIST < last) ? k + 1 + DIST : last);
+      if constexpr (early) __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_wave_barrier();
       PHY_STAMP(k, 4)
 
@@ -523,11 +579,7 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       if constexpr (G > 1)
       { // the maximum runs over all categories of the pattern (src/avx.c:498-503): combine the category groups
         // (not for mixture classes: a class tree rescales on its own, src/mixt.c:2603-2640)
-        if (!cls)
-        {
-#pragma unroll
-          for (int d = PW; d < 64; d <<= 1) mxh = max(mxh, (unsigned)__shfl_xor((int)mxh, d, 64));
-        }
+        if (!cls) mxh = group_max(mxh);
       }
       unsigned sc = s1 + s2; // src/avx.c:462-464
       if (mxh < kHiInvTwoToLarge && q.apply_scaling)
@@ -556,21 +608,21 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
 
     if constexpr (ARGS != 0)
     {
-      step(0, 0, RA, PA, PA2, FA, scA, FB, scB);
+      step(0, 0, RA, PA, PA2, PB, PB2, FA, scA, FB, scB);
       if constexpr (single)
       { // the evaluation below expects the last result in the second register set
 #pragma unroll
         for (int e = 0; e < CS; ++e) FB[e] = FA[e];
         scB = scA;
       }
-      else step(1, 1, RB, PB, PB2, FB, scB, FA, scA);
+      else step(1, 1, RB, PB, PB2, PA, PA2, FB, scB, FA, scA);
     }
     else
       for (int k = 0; k < q.n_ops; k += 2)
       {
-        step(k, 0, RA, PA, PA2, FA, scA, FB, scB);
-        if constexpr (DIST == 2) step(k + 1, 1, RB, PB, PB2, FB, scB, FA, scA);
-        else step(k + 1, 1, RA, PA, PA2, FB, scB, FA, scA);
+        step(k, 0, RA, PA, PA2, PB, PB2, FA, scA, FB, scB);
+        if constexpr (DIST == 2) step(k + 1, 1, RB, PB, PB2, PA, PA2, FB, scB, FA, scA);
+        else step(k + 1, 1, RA, PA, PA2, PA, PA2, FB, scB, FA, scA);
       }
   }
 
