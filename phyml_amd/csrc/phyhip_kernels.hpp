@@ -1408,7 +1408,9 @@ __device__ __forceinline__ void dlk_lane(const DlkParams &q, const DlkCall &k, c
         }
         else
         {
-          lk  = lk * (1. - k.pinvar) + inv * k.pinvar;
+          // (one rounding, as the reference's binary and the CPU restatement under oracle/ take it: both contract
+          // lk * (1 - pinvar) + inv * pinvar -- the per-pattern dlk / lk is held to their bits, tests/test_gpu_eigen_terms.py)
+          lk  = __builtin_fma(lk, 1. - k.pinvar, inv * k.pinvar);
           dlk = dlk * (1. - k.pinvar);
         }
       }
@@ -1754,6 +1756,10 @@ struct MixParams
   FinishParams  fin;
 };
 
+// x / pow(2, sum) of src/mixt.c:1051 / :3189-3197 for 0 <= sum <= 1024 (beyond, the caller has made it 1023): an exact
+// power-of-two scaling -- but pow(2, 1024) is inf, so at exactly 1024 the reference divides by inf and the class drops out
+__device__ __forceinline__ double mix_unscale(const double x, const int sum) { return sum >= 1024 ? x / __builtin_huge_val() : ldexp(x, -sum); }
+
 static __global__ __launch_bounds__(256) void mixture_combine_kernel(const MixParams q)
 {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1765,7 +1771,7 @@ static __global__ __launch_bounds__(256) void mixture_combine_kernel(const MixPa
     {
       int s = q.fact[k][p];
       if (s > 1024) { s = 1023; raise_warn(q.fin.warn); }
-      const double x = ldexp(q.site_cat[k][(size_t)p * q.cat_stride[k]], -s); // == site_lk_cat / pow(2, sum): exact power-of-two scaling
+      const double x = mix_unscale(q.site_cat[k][(size_t)p * q.cat_stride[k]], s);
       site_lk += x * q.proba[k] * q.r_w[k] / q.r_sum * q.e_w[k] / q.e_sum / q.sum_probas;
     }
     if (q.invar_model)
@@ -1777,7 +1783,9 @@ static __global__ __launch_bounds__(256) void mixture_combine_kernel(const MixPa
     if (site_lk < kSmall) { site_lk = kSmall; raise_warn(q.fin.warn); }
     const double lsl = log(site_lk);
     if (q.site_lnl) q.site_lnl[p] = lsl;
-    contrib = q.wght[p] * lsl; // src/mixt.c:1133 (zero-weight patterns contribute 0)
+    // src/mixt.c:1133.  A pattern without weight adds nothing: the reference never evaluates its classes (site_lk_cat = 0, :998-1003),
+    // here their likelihoods are whatever the class kernels left -- 0 * log(NaN) must not reach the sum
+    contrib = q.wght[p] > kSmall ? q.wght[p] * lsl : 0.0;
   }
   __shared__ double ws[4];
 #pragma unroll
@@ -1841,9 +1849,13 @@ template <int S> __global__ __launch_bounds__(256) void mixture_dlk_kernel(const
         z3 = __builtin_fma(v.y, ex[4 * i + 3], z3);
       }
       int sum = (q.scale_l[k] ? q.scale_l[k][p] : 0) + (q.scale_r[k] ? q.scale_r[k][p] : 0);
-      if (sum > 1024) { sum = 1023; raise_warn(q.fin.warn); }
-      const double lk  = ldexp(z0 + z2, -sum); // == / pow(2, sum)
-      const double dlk = ldexp(z1 + z3, -sum);
+      if (sum > 1024)
+      { // (inside the reference's test of the pattern's weight, src/mixt.c:3144-3198: a pattern without weight raises nothing)
+        sum = 1023;
+        if (wt > kSmall) raise_warn(q.fin.warn);
+      }
+      const double lk  = mix_unscale(z0 + z2, sum);
+      const double dlk = mix_unscale(z1 + z3, sum);
       if (wt > kSmall)
       {
         site_lk  += lk * q.proba[k] * q.r_w[k] / q.r_sum * q.e_w[k] / q.e_sum / q.sum_probas;

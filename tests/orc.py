@@ -77,6 +77,55 @@ class Model:
         self.datatype = int(d["datatype"][0])
 
 
+def _slices(P, ns, ncatg, wght, dot_prod, invar, fact, patterns):
+    """One-pattern views of the per-pattern inputs of an eigen-basis evaluation (orc_dlk / orc_lk_eigen take P and plain arrays)."""
+    wght = f64(wght); dot = f64(dot_prod).reshape(P, ncatg * ns)
+    inv = None if invar is None else np.ascontiguousarray(invar, dtype=np.int16)
+    fct = np.ascontiguousarray(fact, dtype=np.int32)
+    for p in (range(P) if patterns is None else patterns):
+        p = int(p)
+        yield p, wght[p:p + 1], dot[p:p + 1], (None if inv is None else inv[p:p + 1]), fct[p:p + 1]
+
+
+def dlk_terms(l, ns, ncatg, wght, dot_prod, m, invar, fact, apply_scaling, patterns=None):
+    """The per-pattern terms of orc_dlk: the function called on one-pattern slices, so that its two sums are pattern p's
+    wght * (log(lk) - LOG2 * fact) and wght * dlk / lk exactly.  m: a Model (eigenvalues, rates, weights, length bounds, +I).
+    patterns: the patterns wanted (the others stay 0).  Returns (clamped l, lnL terms [P], dlnL terms [P])."""
+    P = len(wght)
+    a, b = np.zeros(P), np.zeros(P)
+    lv = C.c_double(l)
+    fn = lib().orc_dlk
+    for p, w1, d1, i1, f1 in _slices(P, ns, ncatg, wght, dot_prod, invar, fact, patterns):
+        lv = C.c_double(l); lnl = C.c_double(0); dlnl = C.c_double(0)
+        fn(C.byref(lv), C.c_int(1), C.c_int(ncatg), C.c_int(ns), _p(w1), _p(d1), _p(m.e_val), _p(m.gamma_rr), _p(m.gamma_r_proba),
+           C.c_double(m.br_len_mult), C.c_double(m.l_min), C.c_double(m.l_max), C.c_int(m.invar_model), C.c_double(m.pinvar),
+           _p(i1), _p(m.pi), _p(f1), C.c_int(apply_scaling), C.byref(lnl), C.byref(dlnl))
+        a[p], b[p] = lnl.value, dlnl.value
+    if P == 0 or (patterns is not None and len(patterns) == 0):
+        lv = C.c_double(min(max(l, m.l_min), m.l_max))
+    return lv.value, a, b
+
+
+def lk_eigen_terms(l, ns, ncatg, wght, dot_prod, m, invar, fact, apply_scaling, patterns=None):
+    """The per-pattern terms of orc_lk_eigen (see dlk_terms): lnL terms [P]."""
+    P = len(wght)
+    a = np.zeros(P)
+    fn = lib().orc_lk_eigen
+    for p, w1, d1, i1, f1 in _slices(P, ns, ncatg, wght, dot_prod, invar, fact, patterns):
+        a[p] = fn(C.c_double(l), C.c_int(1), C.c_int(ncatg), C.c_int(ns), _p(w1), _p(d1), _p(m.e_val), _p(m.gamma_rr),
+                  _p(m.gamma_r_proba), C.c_double(m.br_len_mult), C.c_double(m.l_min), C.c_double(m.l_max),
+                  C.c_int(m.invar_model), C.c_double(m.pinvar), _p(i1), _p(m.pi), _p(f1), C.c_int(apply_scaling))
+    return a
+
+
+def ordered_sum(terms):
+    """Left-to-right double sum from 0.0: the order in which the oracle (and the reference) adds its per-pattern terms."""
+    s = 0.0
+    for t in np.asarray(terms, dtype=np.float64).tolist():
+        s = s + t
+    return s
+
+
 class OracleTree:
     def __init__(self, model: Model, n_otu, edge_left, edge_rght, edge_len, wght, tip_vec, tip_d_state, tip_is_ambigu,
                  invar=None, apply_scaling=1, arith=1, pmats=None):
@@ -268,6 +317,16 @@ class OracleTree:
                                   C.c_double(m.br_len_mult), C.c_double(m.l_min), C.c_double(m.l_max),
                                   C.c_int(m.invar_model), C.c_double(m.pinvar), _p(self.invar), _p(m.pi),
                                   _p(self.fact_sum_scale), C.c_int(self.apply_scaling))
+
+    def dlk_terms(self, l, patterns=None):
+        """orc_dlk pattern by pattern: (clamped l, lnL terms [P], dlnL terms [P]); added in site order the terms are dlk()'s sums."""
+        m = self.m
+        return dlk_terms(l, m.ns, m.ncatg, self.wght, self.dot_prod, m, self.invar, self.fact_sum_scale, self.apply_scaling, patterns)
+
+    def lk_eigen_terms(self, l, patterns=None):
+        """orc_lk_eigen pattern by pattern: lnL terms [P]; added in site order they are lk_eigen()'s sum."""
+        m = self.m
+        return lk_eigen_terms(l, m.ns, m.ncatg, self.wght, self.dot_prod, m, self.invar, self.fact_sum_scale, self.apply_scaling, patterns)
 
 
 def tree_from_golden(d, arith=1, use_dumped_pmats=False):

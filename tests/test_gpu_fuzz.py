@@ -61,6 +61,6 @@ def test_random_configuration(ns, i):
                 lv, la = t.dLk(l, e)
                 da = t.c_dlnL
                 _, lb, db = ot.dlk(l)
-                assert abs(la - lb) <= tol * abs(lb) and abs(da - db) <= 1e-8 * max(1.0, abs(db)), (c, e, l, la, lb, da, db)
+                assert abs(la - lb) <= tol * abs(lb) and abs(da - db) <= 1e-12 * max(1.0, abs(db)), (c, e, l, la, lb, da, db)
     finally:
         t.close()

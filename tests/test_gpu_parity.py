@@ -95,7 +95,7 @@ def test_eigen_lr_and_dlk(name, evaluated):
             l_out, lnl = t.dLk(l_in, e)
             assert l_out == l_in
             assert abs(lnl - lnl_ref) / abs(lnl_ref) < 1e-12
-            assert abs(t.c_dlnL - dlnl_ref) <= 1e-8 * max(1.0, abs(dlnl_ref))
+            assert abs(t.c_dlnL - dlnl_ref) <= 1e-12 * max(1.0, abs(dlnl_ref)), (t.c_dlnL, dlnl_ref)
         assert abs(t.Lk(e) - d[f"eig_lnL_{e}"][0]) / abs(d[f"eig_lnL_{e}"][0]) < 1e-12
         t.Set_Use_Eigen_Lr(False)
 
