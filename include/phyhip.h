@@ -239,6 +239,37 @@ int phyhip_calculate_edge_site_outputs_exact(int instance, int parentBufferIndex
                                              double *unscaled_site_lk_cat, int *fact_sum_scale,
                                              double *outSumLogLikelihood, int *outNumericalWarning);
 
+/* The marginal posterior of every state at internal nodes -- the site loop of Ancestral_Sequences_One_Node (src/ancestral.c:609-901,
+   what `phyml --ancestral` prints) -- evaluated on the device for a list of nodes in one launch, so that only the answer crosses
+   the link instead of every partial and scale vector of the tree (phyhip_get_partials / phyhip_get_scale_factors).
+     Node k has neighbours v_0..v_2 over edges b_0..b_2.  sideBufferIndices[3k+j]: the partials buffer of b_j on v_j's side
+   (v_j == b_j->left ? p_lk_left : p_lk_rght), or v_j's tip index where v_j is a tip; probabilityIndices[3k+j]: the matrix of b_j
+   ([category][i][j], as everywhere).  Per pattern p and state i:
+       x_j(c,i) = sum_s side_j[p][c][s] * Pij_j[c][i][s]      (a tip: its allowed-state 0/1 vector in every category)
+       q[i]     = sum_c x_0 x_1 x_2 pi[i] gamma_r_proba[c];   ss = the scale exponents of the non-tip sides at p, added
+       +I:        q[i] = q[i] (1 - pinvar) + Invariant_Lk(ss, p) pinvar pi[i]; where Invariant_Lk overflowed (-> *outNumericalWarning
+                  = 1) q[i] = Invariant_Lk(0, p) pinvar pi[i]                                   (src/ancestral.c:843-865)
+       outPosteriors[k][p][i] = exp(log(q[i]) - LOG2 ss - c_lnL_sorted[p])                     (src/ancestral.c:868-870)
+   inSiteLogLikelihoods: c_lnL_sorted [pattern], or NULL for what the instance's last edge evaluation left on the device
+   (phyhip_get_site_log_likelihoods) -- the reference runs this after Set_Both_Sides(YES); Lk(NULL) (src/main.c:281-288).
+     Precondition as in the reference: the partials on all three sides of every node are current (queued operations are executed
+   first, virtual buffers stored).  Rows of patterns whose weight is not above SMALL are written as 0 (the reference reads stale
+   vectors there).  *outNumericalWarning (may be NULL) is 0 unless Invariant_Lk overflowed at some pattern.  nodeCount == 0 succeeds.
+     NO bit parity with the reference's binary is claimed for this call: the reference's products run in plain C order under -O3
+   contraction, which nothing pins; this kernel's order of additions is its own.  It is held to the formula above at 1e-10
+   relative per entry; log and exp are the reference's libm's.  MPEE_Infer is a host function of the result and stays with the caller.
+     Nothing else changes: partials, scale vectors, matrices, the outputs of the last evaluation, the numerical warning and what
+   the next evaluation returns stay what they were.  The result's device work space (nodeCount x patternCount x stateCount
+   doubles) is allocated or grown on use and kept; if it cannot be had: PHYHIP_ERROR_OUT_OF_MEMORY -- ask for fewer nodes per call.
+     Sharded instance: each shard computes its pattern range and the rows land at their global pattern positions; sharding changes
+   no bit of the result.  One-process-per-GPU form (phyhip_comm_init_rank): LOCAL to the rank, no collective.
+     Bad side or matrix indices: PHYHIP_ERROR_OUT_OF_RANGE.  Instances created with PHYHIP_FLAG_CLASS_AXIS or
+   PHYHIP_FLAG_GENERIC_LOOP: PHYHIP_ERROR_NO_IMPLEMENTATION.  1 .. 64 categories, 4 or 20 states. */
+int phyhip_calculate_node_state_posteriors(int instance, int nodeCount,
+                                           const int *sideBufferIndices, const int *probabilityIndices,
+                                           const double *inSiteLogLikelihoods, double *outPosteriors,
+                                           int *outNumericalWarning);
+
 /* replaces beagleGetPartials, src/beagle_utils.c:252 (download hook for ancestral.c, cv.c, m4.c ...) */
 int phyhip_get_partials(int instance, int bufferIndex, int scaleIndex, double *outPartials);
 
@@ -365,6 +396,10 @@ int phyhip_profile_read_traffic(int instance, double *outReadBytes, double *outW
 /* The eigen-basis kernels launched since phyhip_profile(instance, 1): Update_Eigen_Lr's kernel (src/lk.c:1038) and the
    dLk / eigen-basis Lk kernel (src/lk.c:655-753), milliseconds and launches of each (HIP events on the instance's stream). */
 int phyhip_profile_read_eigen(int instance, double *outEigenLrMs, int *outEigenLrLaunches, double *outDlkMs, int *outDlkLaunches);
+/* The kernel of phyhip_calculate_node_state_posteriors while the instance is being profiled: milliseconds (HIP events on the
+   instance's stream, uploads and the download of the result excluded) and calls since the previous read; reading resets both.
+   Sharded instances: added over the shards. */
+int phyhip_profile_read_node_posteriors(int instance, double *outKernelMs, int *outCalls);
 
 /* The resident evaluators (small nucleotide alignments, scalar wanted on the host): the launch-bound calls of a search --
    the chain of dLk calls of a branch-length optimisation (src/optimiz.c: Br_Len_Opt) and the short evaluations of SPR

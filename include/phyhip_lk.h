@@ -178,6 +178,17 @@ void Get_Site_Lk(t_tree *tree, phydbl *c_lnL_sorted, phydbl *cur_site_lk, phydbl
 phydbl Get_Exact_Site_Lk(t_tree *tree, t_edge *b, phydbl *c_lnL_sorted, phydbl *cur_site_lk, phydbl *unscaled_site_lk_cat,
                          int *fact_sum_scale);
 
+/* The marginal posterior of every state at internal node d, per pattern (phyhip_calculate_node_state_posteriors): the site loop of
+   Ancestral_Sequences_One_Node (src/ancestral.c:609-901) on the device.  The three (partial vector, matrix) pairs are resolved as
+   there (src/ancestral.c:661-706: v_k == b_k->left ? left : rght; a tip is its tip index).  As in the reference (src/main.c:281-288)
+   the caller has run Set_Both_Sides(YES); Lk(NULL): every partial is current and the per-site log-likelihoods on the device are the
+   tree's.  probs: [n_pattern][ns].  Afterwards the reference's check (src/ancestral.c:878-885): a weighted pattern whose
+   probabilities are not within 0.01 of summing to 1 goes through the exit handler.  No bit parity with the reference's binary is
+   claimed (include/phyhip.h).  Not built: rooted trees (tree->e_root) and mixture trees; MPEE_Infer stays with the caller. */
+void Get_Ancestral_Probs(t_tree *tree, t_node *d, phydbl *probs);
+/* ... of all internal nodes in ONE device call: probs [n_otu - 2][n_pattern][ns], row k = a_nodes[n_otu + k] */
+void Get_All_Ancestral_Probs(t_tree *tree, phydbl *probs);
+
 void Set_Exit_Handler(void (*handler)(const char *msg));
 
 #ifdef __cplusplus

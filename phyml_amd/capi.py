@@ -47,7 +47,7 @@ SYMBOLS = [
     "phyhip_calculate_mixture_eigen_lnl_dlnl", "phyhip_comm_get_unique_id", "phyhip_comm_init_rank", "phyhip_comm_size",
     "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_calculate_class_mixture_log_likelihood",
     "phyhip_calculate_class_mixture_eigen_lnl_dlnl", "phyhip_get_class_scale_factors", "phyhip_set_mixture_invariant_sites",
-    "phyhip_calculate_edge_site_outputs_exact",
+    "phyhip_calculate_edge_site_outputs_exact", "phyhip_calculate_node_state_posteriors", "phyhip_profile_read_node_posteriors",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -239,6 +239,24 @@ class Instance:
         _chk(self.L.phyhip_calculate_edge_site_outputs_exact(self.id, int(parent), int(child), int(pmat), _ptr(a), _ptr(b), _ptr(c),
                                                              _ptr(f), C.byref(s), C.byref(w)))
         return a, b, c, f, s.value, w.value
+
+    def node_state_posteriors(self, sides, matrices, site_lnl=None, with_warning=False):
+        """phyhip_calculate_node_state_posteriors: the marginal state posteriors [node][pattern][state] of the internal nodes whose
+        three (side buffer or tip, matrix) pairs are the rows of `sides` / `matrices` ([node][3]); site_lnl: c_lnL_sorted, or None
+        for what the instance's last edge evaluation left on the device.  with_warning: (posteriors, numerical warning)."""
+        s = np.ascontiguousarray(sides, dtype=np.int32).reshape(-1, 3); m = np.ascontiguousarray(matrices, dtype=np.int32).reshape(-1, 3)
+        assert s.shape == m.shape
+        l = None if site_lnl is None else _f64(site_lnl)
+        assert l is None or l.size == self.P
+        out = np.zeros((s.shape[0], self.P, self.S)); w = C.c_int(0)
+        _chk(self.L.phyhip_calculate_node_state_posteriors(self.id, int(s.shape[0]), _ptr(s), _ptr(m), _ptr(l), _ptr(out), C.byref(w)))
+        return (out, w.value) if with_warning else out
+
+    def profile_read_node_posteriors(self):
+        """(ms, calls) of the kernel of node_state_posteriors since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0)
+        _chk(self.L.phyhip_profile_read_node_posteriors(self.id, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def get_partials(self, buf):
         out = np.zeros((self.P, self.C * self.S))

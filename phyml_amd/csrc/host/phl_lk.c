@@ -16,6 +16,7 @@
 #include <string.h>
 
 #define SMALL_PIJ 1.E-100 /* src/utilities.h:478 */
+#define SMALL 2.2250738585072014e-308 /* DBL_MIN, src/utilities.h:476 */
 
 static void (*g_exit_handler)(const char *) = NULL;
 
@@ -762,4 +763,59 @@ phydbl Get_Exact_Site_Lk(t_tree *tree, t_edge *b, phydbl *c_lnL_sorted, phydbl *
   CHKV(phyhip_calculate_edge_site_outputs_exact(tree->b_inst, left, rght, b->Pij_rr_idx, c_lnL_sorted, cur_site_lk,
                                                 unscaled_site_lk_cat, fact_sum_scale, &lnl, NULL), 0.0);
   return lnl;
+}
+
+/* src/ancestral.c:661-706: the partial vector of b_k on v_k's side (a tip: its tip index) and the matrix of b_k, k = 0..2 */
+static void Ancestral_Indices(const t_node *d, int *sides, int *mats)
+{
+  for (int k = 0; k < 3; ++k)
+  {
+    const t_node *v = d->v[k];
+    const t_edge *b = d->b[k];
+    sides[k] = v->tax ? v->num : (v == b->left ? b->p_lk_left_idx : b->p_lk_rght_idx);
+    mats[k]  = b->Pij_rr_idx;
+  }
+}
+
+/* src/ancestral.c:878-885 over n_nodes rows of [n_pattern][ns]; NO: the exit handler was called */
+static int Ancestral_Check_Sums(const t_tree *tree, const phydbl *probs, int n_nodes)
+{
+  const int ns = tree->mod->ns;
+  for (int k = 0; k < n_nodes; ++k)
+    for (int site = 0; site < tree->n_pattern; ++site)
+    {
+      if (!(tree->wght[site] > SMALL)) continue;
+      const phydbl *p = probs + ((size_t)k * tree->n_pattern + site) * ns;
+      phydbl sum_probas = 0.0;
+      for (int i = 0; i < ns; ++i) sum_probas += p[i];
+      if (!(fabs(sum_probas - 1.0) < 0.01)) /* Are_Equal(sum_probas,1.0,0.01) == NO */
+      {
+        Lk_Exit("Ancestral_Sequences_One_Node", "Probabilities do not sum to 1.0! Aborting.");
+        return NO;
+      }
+    }
+  return YES;
+}
+
+void Get_Ancestral_Probs(t_tree *tree, t_node *d, phydbl *probs)
+{
+  int sides[3], mats[3];
+  if (tree->e_root) { Lk_Exit("Get_Ancestral_Probs", "rooted trees are not built"); return; }
+  if (d->tax) { Lk_Exit("Get_Ancestral_Probs", "a tip has no ancestral state probabilities"); return; }
+  Ancestral_Indices(d, sides, mats);
+  CHK(phyhip_calculate_node_state_posteriors(tree->b_inst, 1, sides, mats, NULL, probs, NULL));
+  Ancestral_Check_Sums(tree, probs, 1);
+}
+
+void Get_All_Ancestral_Probs(t_tree *tree, phydbl *probs)
+{
+  const int n = tree->n_otu - 2;
+  if (tree->e_root) { Lk_Exit("Get_All_Ancestral_Probs", "rooted trees are not built"); return; }
+  int *idx = (int *)calloc((size_t)(n > 0 ? n : 1) * 6, sizeof(int));
+  if (!idx) { Lk_Exit("Get_All_Ancestral_Probs", "out of memory"); return; }
+  for (int k = 0; k < n; ++k) Ancestral_Indices(tree->a_nodes[tree->n_otu + k], idx + 3 * k, idx + 3 * n + 3 * k);
+  const int rc = phyhip_calculate_node_state_posteriors(tree->b_inst, n, idx, idx + 3 * n, NULL, probs, NULL);
+  free(idx);
+  if (rc < 0) { Lk_Exit("phyhip_calculate_node_state_posteriors", phyhip_get_last_error()); return; }
+  Ancestral_Check_Sums(tree, probs, n);
 }

@@ -14,6 +14,7 @@
 //   * log and exp the reference's libm's (phyhip_log.hpp, phyhip_exp.hpp).
 // It writes buffers of its own: what the evaluation kernels left (site outputs, warning flag, results) stays as it was.
 #include "phyhip_host.hpp"
+#include "phyhip_layout.hpp"
 #include "phyhip_log.hpp"
 
 namespace phyhip_host
@@ -33,19 +34,15 @@ struct ExactParams
   double          pinvar;
 };
 
-// element offset of (pattern, category, state) inside internal buffer b (dev_off of phyhip_host.hpp, for the device)
+// (phyhip_layout.hpp)
 template <int S> __device__ __forceinline__ size_t exact_off(const ExactParams &q, int b, long long p, int c, int s)
 {
-  if (S == 20 && q.layout == 1) return (size_t)b * aa_buf_elems(q.Ppad, q.C) + aa_off(p, q.C, c, s);
-  if (S == 4 && q.layout == 2)
-    return (size_t)b * ((size_t)q.Ppad * q.C * S) + ((size_t)(c * 2 + (s >> 1)) * q.Ppad + (size_t)p) * 2 + (size_t)(s & 1);
-  return (((size_t)b * q.P + (size_t)p) * q.C + c) * S + s;
+  return partial_off<S>(q.layout, q.P, q.Ppad, q.C, b, p, c, s);
 }
 
 template <int S> __device__ __forceinline__ uint32_t exact_tip_mask(const ExactParams &q, int tip, long long p)
 {
-  const uint32_t code = q.tip_codes[(size_t)tip * q.Ppad + p];
-  return (S <= 8) ? code : q.code_masks[code];
+  return tip_state_mask<S>(q.tip_codes, q.code_masks, q.Ppad, tip, p);
 }
 
 // One lane per pattern.  20 states: the category's matrix (400 doubles) is staged in LDS by the workgroup, category after
@@ -210,7 +207,7 @@ static int exact_run(Instance *I, int parent, int child, int pm, double *lnl, do
   q.tip_codes = I->d_tipcodes; q.code_masks = I->d_masks; q.wght = I->d_wght; q.pi = I->d_pi; q.cat_w = I->d_catw; q.invar = I->d_invar;
   q.site_lnl = (double *)I->d_exact; q.site_lk = q.site_lnl + P; q.site_cat = q.site_lk + P;
   q.fact = (int *)(q.site_cat + P * (size_t)I->C); q.warn = q.fact + P;
-  q.P = I->P; q.Ppad = I->Ppad; q.C = I->C; q.tips = I->tips; q.layout = I->perm ? 1 : (I->soa ? 2 : 0);
+  q.P = I->P; q.Ppad = I->Ppad; q.C = I->C; q.tips = I->tips; q.layout = layout_of(I);
   q.parent = parent; q.child = child; q.apply_scaling = I->apply_scaling; q.invar_model = I->invar_model; q.pinvar = I->pinvar;
   HIPCHK(hipMemsetAsync(q.warn, 0, sizeof(int), I->stream));
   const double *pmat = I->d_pmats + (size_t)pm * I->C * I->S * I->S;

@@ -9,6 +9,7 @@
 //   phyhip_shard.hip     pattern shards over several devices, the one collective
 //   phyhip_big.hip       instantiations of resident_big_kernel (its own compile flags)
 //   phyhip_exact.hip     the per-pattern outputs of an edge as the reference's doubles (a kernel and an entry point of its own)
+//   phyhip_ancestral.hip the marginal state posteriors of internal nodes (a kernel and an entry point of its own)
 // Internal: nothing here is part of the ABI (include/phyhip.h).
 #pragma once
 #include "../../include/phyhip.h"
@@ -206,6 +207,10 @@ struct Instance
   double   *d_site_lnl = nullptr, *d_site_lk = nullptr, *d_site_cat = nullptr, *d_dot = nullptr;
   int      *d_fact     = nullptr;
   void     *d_exact    = nullptr; // outputs of phyhip_calculate_edge_site_outputs_exact (phyhip_exact.hip), allocated on first use
+  void     *d_anc      = nullptr; // work space of phyhip_calculate_node_state_posteriors (phyhip_ancestral.hip): grown on use, kept
+  size_t    anc_cap    = 0;       // ... its size in bytes
+  double    anc_prof_ms = 0.0;    // while profiling: time of its kernel launches (phyhip_profile_read_node_posteriors)
+  int       anc_prof_n = 0;
   double   *d_block    = nullptr; // [2][grid]
   double   *d_result   = nullptr; // [2]
   double   *h_result   = nullptr; // pinned, device-visible: [0..1] results, [2] sequence number (as u64)

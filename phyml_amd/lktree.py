@@ -209,6 +209,19 @@ class LkTree:
         _raise_if_error()
         return v, a, c, u, f
 
+    def Ancestral_Probs(self, d=None):
+        """Get_Ancestral_Probs(d): the marginal state posteriors [pattern][state] of internal node d; d=None:
+        Get_All_Ancestral_Probs, [n_otu - 2][pattern][state], row k = node n_otu + k.  The partials on every side must be current
+        and the last evaluation's per-site log-likelihoods the tree's (Set_Both_Sides(True); Lk(None))."""
+        if d is None:
+            out = np.zeros((self.n - 2, self.P, self.S))
+            self.L.Get_All_Ancestral_Probs(self.tree, _dp(out))
+        else:
+            out = np.zeros((self.P, self.S))
+            self.L.Get_Ancestral_Probs(self.tree, self.node(d), _dp(out))
+        _raise_if_error()
+        return out
+
     def dLk(self, l, b):
         lv = C.c_double(l)
         v = self.L.dLk(C.byref(lv), self.edge(b), self.tree)
