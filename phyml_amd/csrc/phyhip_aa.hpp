@@ -1260,43 +1260,11 @@ __global__ __launch_bounds__((NT == 2 || RES) ? 64 * (kAaMaxCons2 + 1) : (D2 ? 6
             double site = 0.0;
 #pragma unroll
             for (int cc = 0; cc < C_; ++cc) site += __shfl(lkc, (lane & ~(3 << 2)) | (((b / CB) * CB + cc) << 2), 64) * (ARGS ? pre_cw[cc] : q.cat_w[cc]);
+            // (two roundings in the +I mix, the device library's log: tests/test_gpu_eigen_terms.py; argument form:
+            // weight, invariant state and pi[that state] out of what was requested up front; stores in the form's cache policy)
             if (pact[i] && kk == 0 && c == 0)
-            {
-              const double wt = ARGS ? pre_wt : q.wght[p0[i]];
-              int          f  = q.apply_scaling ? (int)(sl[i] + sr[i]) : 0;
-              if (wt > kSmall)
-              {
-                if (q.invar_model)
-                { // src/lk.c:820-842, 1226-1273
-                  const int iv  = ARGS ? pre_iv : q.invar[p0[i]];
-                  double    inv = 0.0;
-                  bool      issue_ = false;
-                  if (iv >= 0)
-                  {
-                    inv = ARGS ? inv_pre : q.pi[iv];
-                    if (q.apply_scaling)
-                    {
-                      int e = f;
-                      do
-                      {
-                        const int piece = e < 63 ? e : 63;
-                        inv *= (double)(1ull << piece);
-                        e -= piece;
-                      } while (e != 0);
-                    }
-                    issue_ = isinf(inv);
-                  }
-                  if (issue_) { f = 0; site = q.pi[iv] * q.pinvar; }
-                  else site = site * (1. - q.pinvar) + inv * q.pinvar;
-                }
-                if (site < kSmall) { site = kSmall; raise_warn(q); }
-                const double lsl = log(site) - kLog2 * (double)f;
-                if (q.site_lnl) gst(&q.site_lnl[p0[i]], lsl);
-                if (q.site_lk) gst(&q.site_lk[p0[i]], dev_exp(lsl));
-                contrib = wt * lsl;
-              }
-              gst(&q.fact[p0[i]], f);
-            }
+              site_tail<TailMix::two_roundings, TailLibm::device, ARGS ? TailInputs::preloaded : TailInputs::memory>(
+                  contrib, q, (size_t)p0[i], ARGS ? pre_wt : q.wght[p0[i]], site, q.apply_scaling ? (int)(sl[i] + sr[i]) : 0, gst, pre_iv, inv_pre);
             // this TILE's share: fixed shuffle tree -> deterministic, and the same double whichever wave shape computed it
             // (the tree contrib += shfl_down(contrib, 32 / 16 / 8 / 4 / 2 / 1) as lane 0 sees it, without the steps that can only add
             // zeros -- contributions sit in the lanes with kk = 0, c = 0: lanes 0-15, of them block 0 (four categories), blocks 0 and

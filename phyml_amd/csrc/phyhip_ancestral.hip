@@ -122,18 +122,7 @@ __global__ __launch_bounds__(256) void node_posterior_kernel(const AncParams q)
     const int iv = q.invar[p];
     double    inv = 0.0;
     bool      issue = false;
-    if (iv >= 0)
-    {
-      inv = q.pi[iv];
-      if (q.apply_scaling)
-        for (int e = ss; e > 0;)
-        {
-          const int piece = e < 63 ? e : 63;
-          inv *= (double)(1ull << piece);
-          e -= piece;
-        }
-      issue = __builtin_isinf(inv);
-    }
+    if (iv >= 0) invariant_lk(inv, issue, q.pi[iv], ss, q.apply_scaling);
     if (issue)
     {
       *q.warn = 1;

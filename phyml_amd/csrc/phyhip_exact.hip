@@ -148,40 +148,11 @@ __global__ __launch_bounds__(256) void exact_site_kernel(const ExactParams q, co
   // Pull_Scaling_Factors, SCALE_FAST: src/lk.c:2701-2705, 2777-2801
   int f = 0;
   if (q.apply_scaling) f = (ltip ? 0 : scales[(size_t)lb * q.Ppad + p]) + (rtip ? 0 : scales[(size_t)rb * q.Ppad + p]);
-  if (q.invar_model)
-  { // src/lk.c:820-842 with Invariant_Lk, :1226-1273
-    const int iv = q.invar[p];
-    double    inv = 0.0;
-    bool      issue = false;
-    if (iv >= 0)
-    {
-      inv = q.pi[iv];
-      if (q.apply_scaling)
-        for (int e = f; e > 0;)
-        {
-          const int piece = e < 63 ? e : 63;
-          inv *= (double)(1ull << piece);
-          e -= piece;
-        }
-      issue = __builtin_isinf(inv);
-    }
-    if (issue)
-    {
-      f    = 0;
-      site = q.pi[iv] * q.pinvar;
-    }
-    else
-      site = __builtin_fma(site, 1.0 - q.pinvar, inv * q.pinvar);
-  }
-  if (site < kSmall)
-  { // src/lk.c:847-851
-    site    = kSmall;
-    *q.warn = 1;
-  }
-  const double lsl = __builtin_fma(-(double)f, kLog2, phyhip_log_ref(site, phyhip_log_data)); // src/lk.c:854
-  q.site_lnl[p] = lsl;
-  q.site_lk[p]  = phyhip_exp_ref(lsl, phyhip_exp_tab);
-  q.fact[p]     = f;
+  // src/lk.c:820-856 as the reference's binary has it: the +I mix one fused operation, the reference's log / exp with the LOG2 term
+  // fused, every output present (tests/test_gpu_exact_site.py holds them to the reference's bits).  Patterns without weight have
+  // returned above: the weight test passes by construction and the weighted term is not used.
+  double term;
+  site_tail<TailMix::fused, TailLibm::reference>(term, q, (size_t)p, 1.0, site, f, PlainStore());
 }
 
 // One plain instance: its patterns into the caller's arrays (any may be NULL; wght_out receives its pattern weights)

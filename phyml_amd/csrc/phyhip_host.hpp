@@ -10,6 +10,12 @@
 //   phyhip_big.hip       instantiations of resident_big_kernel (its own compile flags)
 //   phyhip_exact.hip     the per-pattern outputs of an edge as the reference's doubles (a kernel and an entry point of its own)
 //   phyhip_ancestral.hip the marginal state posteriors of internal nodes (a kernel and an entry point of its own)
+// The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
+// phyhip_big.hpp, and what they share --
+//   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
+//                        and log, and site_tail, the whole of it (20-state and exact kernels; who still carries a copy: DESIGN §5)
+//   phyhip_layout.hpp    addressing of the three partial layouts and the tip masks (exact and ancestral kernels)
+//   phyhip_exp.hpp, phyhip_log.hpp   the reference libm's exp and log
 // Internal: nothing here is part of the ABI (include/phyhip.h).
 #pragma once
 #include "../../include/phyhip.h"

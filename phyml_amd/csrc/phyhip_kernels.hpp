@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "phyhip_exp.hpp"
+#include "phyhip_log.hpp"
 
 namespace phyhip
 {
@@ -392,6 +393,11 @@ __device__ __forceinline__ void raise_warn(int *warn)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
 }
 
+} // namespace phyhip
+#include "phyhip_tail.hpp" // Lk_Core's per-pattern tail
+namespace phyhip
+{
+
 __device__ __forceinline__ void post_host_block(HostBlock *dst, double sum, unsigned long long tag)
 {
   typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -686,6 +692,8 @@ __global__ __launch_bounds__(256) void traverse_kernel(const TreeParams q, const
     {
       const double w = q.wght[p];
       int          f = q.apply_scaling ? (sl + sr) : 0; // SCALE_FAST, src/lk.c:2777-2794 / :2701-2705
+      // (site_tail<two_roundings, device> of phyhip_tail.hpp, written out: called, the tail compiles to other machine code here, in
+      // traverse_nt_kernel and in nt2_run -- profiles/r10_tail_refactor.md; a change to the tail goes there AND to these three)
       if (w > kSmall)
       {
         if (q.invar_model)
@@ -693,21 +701,7 @@ __global__ __launch_bounds__(256) void traverse_kernel(const TreeParams q, const
           const int iv  = q.invar[p];
           double    inv = 0.0;
           bool      issue = false;
-          if (iv >= 0)
-          {
-            inv = q.pi[iv];
-            if (q.apply_scaling)
-            {
-              int e = f;
-              do
-              {
-                const int piece = e < 63 ? e : 63;
-                inv *= (double)(1ull << piece);
-                e -= piece;
-              } while (e != 0);
-            }
-            issue = isinf(inv);
-          }
+          if (iv >= 0) invariant_lk(inv, issue, q.pi[iv], f, q.apply_scaling);
           if (issue)
           {
             f    = 0;
@@ -1028,28 +1022,14 @@ __global__ __launch_bounds__(256, (DIST == 2 ? 3 : 4)) void traverse_nt_kernel(c
     {
       const double w = q.wght[p];
       int          f = q.apply_scaling ? (sl + sr) : 0;
-      if (w > kSmall)
+      if (w > kSmall) // (site_tail<two_roundings, device> written out: see traverse_kernel)
       {
         if (q.invar_model)
         {
           const int iv = q.invar[p];
           double    inv = 0.0;
           bool      issue_ = false;
-          if (iv >= 0)
-          {
-            inv = q.pi[iv];
-            if (q.apply_scaling)
-            {
-              int e = f;
-              do
-              {
-                const int piece = e < 63 ? e : 63;
-                inv *= (double)(1ull << piece);
-                e -= piece;
-              } while (e != 0);
-            }
-            issue_ = isinf(inv);
-          }
+          if (iv >= 0) invariant_lk(inv, issue_, q.pi[iv], f, q.apply_scaling);
           if (issue_) { f = 0; site = q.pi[iv] * q.pinvar; }
           else site = site * (1. - q.pinvar) + inv * q.pinvar;
         }
@@ -1386,21 +1366,7 @@ __device__ __forceinline__ void dlk_lane(const DlkParams &q, const DlkCall &k, c
         const int iv  = in.iv;
         double    inv = 0.0;
         bool      issue = false;
-        if (iv >= 0)
-        {
-          inv = q.pi[iv];
-          if (k.apply_scaling)
-          {
-            int e = f;
-            do
-            {
-              const int piece = e < 63 ? e : 63;
-              inv *= (double)(1ull << piece);
-              e -= piece;
-            } while (e != 0);
-          }
-          issue = isinf(inv);
-        }
+        if (iv >= 0) invariant_lk(inv, issue, q.pi[iv], f, k.apply_scaling);
         if (issue)
         {
           if (k.with_derivative) { lk = inv * k.pinvar; dlk = 0.0; }
@@ -1410,12 +1376,12 @@ __device__ __forceinline__ void dlk_lane(const DlkParams &q, const DlkCall &k, c
         {
           // (one rounding, as the reference's binary and the CPU restatement under oracle/ take it: both contract
           // lk * (1 - pinvar) + inv * pinvar -- the per-pattern dlk / lk is held to their bits, tests/test_gpu_eigen_terms.py)
-          lk  = __builtin_fma(lk, 1. - k.pinvar, inv * k.pinvar);
+          lk  = mix_invariant<TailMix::fused>(lk, inv, k.pinvar);
           dlk = dlk * (1. - k.pinvar);
         }
       }
       if (lk < kSmall)
-      {
+      { // (floored_log<device> of phyhip_tail.hpp written out, its log two lines down: called, dlk_kernel schedules differently)
         lk = kSmall;
         raise_warn(warn);
       }

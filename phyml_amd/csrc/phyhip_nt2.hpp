@@ -753,28 +753,14 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
     {
       const double w = w_pre;
       int          f = q.apply_scaling ? (int)(sl + sr) : 0;
-      if (w > kSmall)
+      if (w > kSmall) // (site_tail<two_roundings, device> of phyhip_tail.hpp written out: see traverse_kernel)
       {
         if (q.invar_model)
         {
           const int iv = iv_pre;
           double    inv = 0.0;
           bool      issue_ = false;
-          if (iv >= 0)
-          {
-            inv = q.pi[iv];
-            if (q.apply_scaling)
-            {
-              int e = f;
-              do
-              {
-                const int piece = e < 63 ? e : 63;
-                inv *= (double)(1ull << piece);
-                e -= piece;
-              } while (e != 0);
-            }
-            issue_ = isinf(inv);
-          }
+          if (iv >= 0) invariant_lk(inv, issue_, q.pi[iv], f, q.apply_scaling);
           if (issue_) { f = 0; site = q.pi[iv] * q.pinvar; }
           else site = site * (1. - q.pinvar) + inv * q.pinvar;
         }

@@ -316,7 +316,9 @@ def test_per_pattern_terms_sharded(S, Cc, P, shards, monkeypatch):
 
 # ---- 2: the tail's branches on the routes a search uses ----------------------------------------------------------------------------
 TAILS = [(4, 4, "traverse_nt2_kernel"), (4, 3, "traverse_nt2_kernel"), (20, 4, "20-state kernel"), (20, 1, "20-state kernel"),
-         (4, 5, "generic kernel"), (4, 12, "generic kernel"), (20, 5, "generic kernel"), (20, 12, "generic kernel")]
+         (4, 5, "generic kernel"), (4, 12, "generic kernel"), (20, 5, "generic kernel"), (20, 12, "generic kernel"),
+         # (the tail is instantiated per category count)
+         (4, 2, "traverse_nt2_kernel"), (4, 1, "traverse_nt2_kernel"), (20, 2, "20-state kernel"), (20, 3, "20-state kernel")]
 
 
 @pytest.mark.parametrize("scaling", [1, 0])

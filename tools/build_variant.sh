@@ -7,7 +7,7 @@ name=$1; shift
 mkdir -p phyml_amd/lib_$name/obj
 F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC"
 objs=""
-for u in phyhip phyhip_queue phyhip_resident phyhip_eigen phyhip_mixture phyhip_shard phyhip_exact; do
+for u in phyhip phyhip_queue phyhip_resident phyhip_eigen phyhip_mixture phyhip_shard phyhip_exact phyhip_ancestral; do
   /opt/rocm/bin/hipcc $F "$@" -c -o phyml_amd/lib_$name/obj/$u.o phyml_amd/csrc/$u.hip &
   objs="$objs phyml_amd/lib_$name/obj/$u.o"
 done
