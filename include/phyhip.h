@@ -270,6 +270,65 @@ int phyhip_calculate_node_state_posteriors(int instance, int nodeCount,
                                            const double *inSiteLogLikelihoods, double *outPosteriors,
                                            int *outNumericalWarning);
 
+/* The pairwise maximum-likelihood distance matrix that BioNJ turns into the starting tree: ML_Dist (src/lk.c:1783-1906) with
+   Lk_Dist (src/lk.c:2416-2473) under Opt_Dist_F / Dist_F_Brent (src/optimiz.c:1848-1972), started from K80_dist / JC69_Dist
+   (src/utilities.c:2407-2587) -- what Dist_And_BioNJ runs on every run without -u, Add_BioNJ_Branch_Lengths, and every bootstrap
+   replicate (src/utilities.c:4000, src/mpi_boot.c:177) -- evaluated on the device from the tips the instance holds.  For every pair
+   of tips j < k, with ONE rate category of rate 1 and weight 1 (ML_Dist forces this: the instance's category rates and weights are
+   ignored):
+       F[s0][s1] = sum of the weights of the patterns where BOTH tips have exactly one allowed state (a one-hot tip vector; on this
+                   ABI B / Z are the single states N / Q); len = sum F; F /= len where len > 0
+       init      = 4 states, K80_dist(data, 1e6): P = transitions / len, Q = transversions / len (both .5 where len == 0);
+                     -1 where 1-2P-Q <= 0 or 1-2Q <= 0, else (g/2)(pow(1-2P-Q,-1/g) + 0.5 pow(1-2Q,-1/g) - 1.5), g = 1e6, at most DIST_MAX = 2
+                   else JC69_Dist: P = mismatches / len (1 where len == 0); -1 where 1 - (S/(S-1))P < 0, else
+                     -((S-1)/S) log(1 - (S/(S-1))P), at most DIST_MAX
+                   then 0.1 where init > DIST_MAX - SMALL or init < 0
+       d         = init where sum F < .001 (no common unambiguous site); else Dist_F_Brent(l_min, max(init, l_min), l_max, 1e-10, 1000)
+                   on -Lk_Dist(F, |u|), which stops when |curr_lnL - old_lnL| < minDiffLk && curr_lnL > init_lnL - minDiffLk
+                   (minDiffLk: mod->s_opt->min_diff_lk_local, 1e-3 by default, src/init.c:770);
+                   Lk_Dist(F, d) = sum_{i<j} (F[i][j] + F[j][i]) log(pi[i] P[i][j]) + sum_i F[i][i] log(pi[i] P[i][i]), P =
+                   PMat_Empirical(d clamped to [l_min, l_max]) of eigen system eigenIndex, SMALL_PIJ floor and row
+                   renormalisation included, pi = frequencies stateFrequenciesIndex
+       outDistances[j][k] = outDistances[k][j] = min(d, DIST_MAX); the diagonal is 0
+   l_min / l_max are those of phyhip_set_phyml_options.  mod->log_l is not served.  Mixtures: the binding picks the class by its
+   eigen index (the reference uses the first class).  Fill_Missing_Dist and BioNJ are O(n^2) / O(n^3) host work without a pattern
+   axis and stay with the caller.
+     The STARTING VALUES are formed on the host side of this library with libm's pow / log, from sums the device reduced: the
+   optimiser stops long before convergence, so its answer follows its starting value one for one, and K80's formula multiplies the
+   last bit of pow by 5e5.  Counting by state departs from the reference's counting by character in two places: K80_dist skips a
+   'U' (here it is the state T), and JC69_Dist counts B against N and Z against Q as mismatches (here they are the same state).
+   A binding that needs those passes its own matrix as inInitialDistances ([tip][tip], K80_dist's / JC69_Dist's output, -1 where
+   the closed form is invalid; only j < k is read); the round trip of the sums is then skipped.
+     Optional outputs (each may be NULL): outInitialDistances [tip][tip], what the closed form gave BEFORE the 0.1 rule;
+   outCounts [pair][state][state], the normalised F, pairs in the order (0,1), (0,2), .., (1,2), ..; outLogLikelihoods [pair],
+   Lk_Dist at the returned distance before the DIST_MAX cap (0 where sum F < .001); outIterations [pair], the iteration of
+   Dist_F_Brent that returned (0 where sum F < .001).
+     Numbers: the raw counts are exact for integer weights and the same bits from run to run for any weights (one fixed order
+   of additions per entry, no atomics); patterns whose weight is not above SMALL contribute nothing.  Matrices, exp and log are
+   the reference's doubles; Lk_Dist's sum runs in the reference's order, so the distances differ from the reference binary's by
+   its compiler's contraction only (1e-9 relative on the reference's own examples).
+     Nothing else changes: partials, scale vectors, matrices, the outputs of the last evaluation and the numerical warning stay
+   what they were, and no queued operation is executed.  The device work space (the raw counts of a band of taxa, at most
+   phyhip_set_pairwise_work_space bytes, and a few doubles per pair) is allocated or grown on use and kept; if it cannot be
+   had: PHYHIP_ERROR_OUT_OF_MEMORY.
+     Sharded instance (one process): each shard counts its patterns on its own device, the raw counts are added in shard order
+   on the first shard's device, the rest runs there.  Instances of phyhip_comm_init_rank (a rank holds only its own patterns),
+   PHYHIP_FLAG_CLASS_AXIS and PHYHIP_FLAG_GENERIC_LOOP instances: PHYHIP_ERROR_NO_IMPLEMENTATION.  Bad eigen / frequency index,
+   minDiffLk <= 0: PHYHIP_ERROR_OUT_OF_RANGE.  4 or 20 states. */
+int phyhip_calculate_pairwise_ml_distances(int instance, int eigenIndex, int stateFrequenciesIndex,
+                                           double minDiffLk,
+                                           const double *inInitialDistances,
+                                           double *outDistances,
+                                           double *outInitialDistances,
+                                           double *outCounts,
+                                           double *outLogLikelihoods,
+                                           int *outIterations);
+
+/* Bound, in bytes, on the raw counts phyhip_calculate_pairwise_ml_distances holds at a time (it walks the taxa in bands of as many
+   as fit, at least one; with more than one band and no inInitialDistances the counts are formed twice).  0: the default, 128 MiB.
+   No result depends on it. */
+int phyhip_set_pairwise_work_space(int instance, long long maxBytes);
+
 /* replaces beagleGetPartials, src/beagle_utils.c:252 (download hook for ancestral.c, cv.c, m4.c ...) */
 int phyhip_get_partials(int instance, int bufferIndex, int scaleIndex, double *outPartials);
 
@@ -400,6 +459,10 @@ int phyhip_profile_read_eigen(int instance, double *outEigenLrMs, int *outEigenL
    instance's stream, uploads and the download of the result excluded) and calls since the previous read; reading resets both.
    Sharded instances: added over the shards. */
 int phyhip_profile_read_node_posteriors(int instance, double *outKernelMs, int *outCalls);
+/* The kernels of phyhip_calculate_pairwise_ml_distances while the instance is being profiled: milliseconds of the count kernels
+   (shard sums and the per-pair sums included) and of the optimiser kernels (HIP events on the instance's stream; the host's
+   starting values and the transfers excluded), and calls since the previous read; reading resets all three. */
+int phyhip_profile_read_pairwise(int instance, double *outCountMs, double *outOptimiseMs, int *outCalls);
 
 /* The resident evaluators (small nucleotide alignments, scalar wanted on the host): the launch-bound calls of a search --
    the chain of dLk calls of a branch-length optimisation (src/optimiz.c: Br_Len_Opt) and the short evaluations of SPR

@@ -189,6 +189,13 @@ void Get_Ancestral_Probs(t_tree *tree, t_node *d, phydbl *probs);
 /* ... of all internal nodes in ONE device call: probs [n_otu - 2][n_pattern][ns], row k = a_nodes[n_otu + k] */
 void Get_All_Ancestral_Probs(t_tree *tree, phydbl *probs);
 
+/* The pairwise ML distance matrix BioNJ starts from -- ML_Dist, src/lk.c:1783-1906, with the reference's own starting values
+   (K80_dist / JC69_Dist by state, formed with the host's libm) -- evaluated on the device (phyhip_calculate_pairwise_ml_distances),
+   for a tree made with Make_Tree_For_Lk whose tips and model are loaded.  min_diff_lk_local: mod->s_opt->min_diff_lk_local (1e-3 by
+   default).  dist: [n_otu][n_otu], symmetric, diagonal 0, at most DIST_MAX.  One category of rate 1, whatever the model's rate
+   classes (ML_Dist forces this).  Fill_Missing_Dist and Bionj stay with the caller. */
+void ML_Dist(t_tree *tree, phydbl min_diff_lk_local, phydbl *dist);
+
 void Set_Exit_Handler(void (*handler)(const char *msg));
 
 #ifdef __cplusplus

@@ -48,6 +48,7 @@ SYMBOLS = [
     "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_calculate_class_mixture_log_likelihood",
     "phyhip_calculate_class_mixture_eigen_lnl_dlnl", "phyhip_get_class_scale_factors", "phyhip_set_mixture_invariant_sites",
     "phyhip_calculate_edge_site_outputs_exact", "phyhip_calculate_node_state_posteriors", "phyhip_profile_read_node_posteriors",
+    "phyhip_calculate_pairwise_ml_distances", "phyhip_set_pairwise_work_space", "phyhip_profile_read_pairwise",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -257,6 +258,38 @@ class Instance:
         ms = C.c_double(0); n = C.c_int(0)
         _chk(self.L.phyhip_profile_read_node_posteriors(self.id, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def pairwise_ml_distances(self, min_diff_lk=1e-3, initial=None, eigen_index=0, frequencies_index=0, want=()):
+        """phyhip_calculate_pairwise_ml_distances: the [tip][tip] ML distance matrix (ML_Dist).  initial: K80_dist's / JC69_Dist's
+        matrix, or None for the closed form from the device's counts.  want: any of "initial" ([tip][tip], before the 0.1 rule),
+        "counts" ([pair][state][state] normalised F), "lnl" ([pair]), "iterations" ([pair]); with a non-empty `want` the result is
+        (distances, {name: array})."""
+        n, npair = self.tips, self.tips * (self.tips - 1) // 2
+        bad = set(want) - {"initial", "counts", "lnl", "iterations"}
+        assert not bad, bad
+        ini = None if initial is None else _f64(initial)
+        assert ini is None or ini.size == n * n
+        out = np.zeros((n, n))
+        extra = {}
+        if "initial" in want: extra["initial"] = np.zeros((n, n))
+        if "counts" in want: extra["counts"] = np.zeros((npair, self.S, self.S))
+        if "lnl" in want: extra["lnl"] = np.zeros(npair)
+        if "iterations" in want: extra["iterations"] = np.zeros(npair, np.int32)
+        fn = self.L.phyhip_calculate_pairwise_ml_distances
+        fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 6
+        _chk(fn(self.id, int(eigen_index), int(frequencies_index), float(min_diff_lk), _ptr(ini), _ptr(out), _ptr(extra.get("initial")),
+                _ptr(extra.get("counts")), _ptr(extra.get("lnl")), _ptr(extra.get("iterations"))))
+        return (out, extra) if want else out
+
+    def set_pairwise_work_space(self, max_bytes):
+        """phyhip_set_pairwise_work_space: bytes of raw counts pairwise_ml_distances holds at a time (0: the default)"""
+        _chk(self.L.phyhip_set_pairwise_work_space(self.id, C.c_longlong(int(max_bytes))))
+
+    def profile_read_pairwise(self):
+        """(count kernels ms, optimiser kernels ms, calls) of pairwise_ml_distances since the previous read, while profile(1)"""
+        a = C.c_double(0); b = C.c_double(0); n = C.c_int(0)
+        _chk(self.L.phyhip_profile_read_pairwise(self.id, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
 
     def get_partials(self, buf):
         out = np.zeros((self.P, self.C * self.S))

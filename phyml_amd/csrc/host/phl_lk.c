@@ -819,3 +819,9 @@ void Get_All_Ancestral_Probs(t_tree *tree, phydbl *probs)
   if (rc < 0) { Lk_Exit("phyhip_calculate_node_state_posteriors", phyhip_get_last_error()); return; }
   Ancestral_Check_Sums(tree, probs, n);
 }
+
+/* ML_Dist (src/lk.c:1783-1906) of the tips the instance holds, on the device (phyhip_calculate_pairwise_ml_distances) */
+void ML_Dist(t_tree *tree, phydbl min_diff_lk_local, phydbl *dist)
+{
+  CHK(phyhip_calculate_pairwise_ml_distances(tree->b_inst, 0, 0, min_diff_lk_local, NULL, dist, NULL, NULL, NULL, NULL));
+}

@@ -10,6 +10,7 @@
 //   phyhip_big.hip       instantiations of resident_big_kernel (its own compile flags)
 //   phyhip_exact.hip     the per-pattern outputs of an edge as the reference's doubles (a kernel and an entry point of its own)
 //   phyhip_ancestral.hip the marginal state posteriors of internal nodes (a kernel and an entry point of its own)
+//   phyhip_dist.hip      the pairwise ML distance matrix, ML_Dist (count, sums and optimiser kernels, an entry point of its own)
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
@@ -174,6 +175,8 @@ struct InlineDef
   bool operator==(const InlineDef &o) const { return a == o.a && b == o.b && pmA == o.pmA && pmB == o.pmB; }
 };
 
+constexpr size_t kDistBandBytes = 128u << 20; // pairwise distances: the raw counts of one band of taxa stay below this by default
+
 struct Instance
 {
   Collective *co         = nullptr; // one-process-per-GPU mode: communicator attached by phyhip_comm_init_rank
@@ -217,6 +220,11 @@ struct Instance
   size_t    anc_cap    = 0;       // ... its size in bytes
   double    anc_prof_ms = 0.0;    // while profiling: time of its kernel launches (phyhip_profile_read_node_posteriors)
   int       anc_prof_n = 0;
+  void     *d_dist     = nullptr; // work space of phyhip_calculate_pairwise_ml_distances (phyhip_dist.hip): grown on use, kept
+  size_t    dist_cap   = 0;       // ... its size in bytes
+  size_t    dist_band_bytes = kDistBandBytes; // ... and the bound on the raw counts held at a time (phyhip_set_pairwise_work_space)
+  double    dist_prof_count_ms = 0.0, dist_prof_opt_ms = 0.0; // while profiling: its count / optimise kernels (phyhip_profile_read_pairwise)
+  int       dist_prof_n = 0;
   double   *d_block    = nullptr; // [2][grid]
   double   *d_result   = nullptr; // [2]
   double   *h_result   = nullptr; // pinned, device-visible: [0..1] results, [2] sequence number (as u64)

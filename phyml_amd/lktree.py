@@ -222,6 +222,13 @@ class LkTree:
         _raise_if_error()
         return out
 
+    def ML_Dist(self, min_diff_lk_local=1e-3):
+        """ML_Dist: the [n_otu][n_otu] pairwise ML distance matrix of the loaded tips under the loaded model, on the device"""
+        out = np.zeros((self.n, self.n))
+        self.L.ML_Dist(self.tree, C.c_double(min_diff_lk_local), _dp(out))
+        _raise_if_error()
+        return out
+
     def dLk(self, l, b):
         lv = C.c_double(l)
         v = self.L.dLk(C.byref(lv), self.edge(b), self.tree)
