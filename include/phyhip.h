@@ -329,6 +329,62 @@ int phyhip_calculate_pairwise_ml_distances(int instance, int eigenIndex, int sta
    No result depends on it. */
 int phyhip_set_pairwise_work_space(int instance, long long maxBytes);
 
+/* SH-like branch supports: the resampling of Statistics_To_SH (src/alrt.c:1148-1298, reached by `-b -4` and `-b -2`) -- and of the
+   deprecated Statistics_to_RELL (src/alrt.c:1091-1140), which falls out of the same pass -- evaluated on the device.  For every
+   internal edge aLRT (src/alrt.c:172-226) runs NNI_Neigh_BL, which stores c_lnL_sorted of the three NNI configurations in
+   log_lks_aLRT[0..2] (src/alrt.c:453,555,682); the statistic then draws 10 000 replicates of init_len sites each: 10 000 x init_len
+   draws per internal edge on one host thread, against three evaluations that take micro- to milliseconds here.
+
+   phyhip_set_support_site_log_likelihoods fills slot 0..2 with one per-pattern vector [pattern]: from the host pointer, or -- NULL --
+   with what the instance's last edge evaluation left on the device (what phyhip_get_site_log_likelihoods would return), device to
+   device, with no download: log_lks_aLRT[slot][site] = c_lnL_sorted[site].  A NULL snapshot executes queued operations first, as
+   that getter does.  The slots (3 x patternCount doubles) are allocated on first use and kept.  Nothing else moves: partials, scale
+   vectors, matrices, the outputs of the last evaluation, the numerical warning and the next evaluation stay what they were. */
+int phyhip_set_support_site_log_likelihoods(int instance, int slot, const double *inSiteLogLikelihoods);
+
+/* The statistic from the three slots.  Weights w: the instance's pattern weights (phyhip_set_pattern_weights); siteCount: data->init_len;
+   replicateCount: 10 000 in the reference.
+       c_k       = sum over the patterns in ascending order of slot_k[p] * w[p] (the rounded product, then the addition;
+                   src/alrt.c:1172-1177): one fixed order of additions.  outTotals[k] = c_k.
+       delta     = the gap between the largest and the second largest of c_0..c_2, by the six-way ordering of src/alrt.c:1184-1216
+                   restated line by line, ties (>=) included
+       replicate r: siteCount draws of a pattern with probability w[p] / sum w;  lk_k = sum over the draws of slot_k[drawn pattern]
+                   (outReplicateSums[r][k], may be NULL: these UNCENTRED sums);  RELL: lk_0 >= lk_1 && lk_0 >= lk_2 (src/alrt.c:1129);
+                   lk_k -= c_k (src/alrt.c:1249-1251);  delta_local by the same ordering of the centred sums (src/alrt.c:1254-1287);
+                   accepted (outAccepted[r] = 0 / 1, may be NULL) when delta > delta_local + 0.1 (src/alrt.c:1289)
+       *outSH    = accepted replicates / replicateCount;  *outRELL = RELL replicates / replicateCount      (each may be NULL)
+   THE ALIAS TABLE is Sample_n_i_With_Proba_pi's (src/stats.c:4493-4560), built operation for operation on the host side of this
+   library in plain sequential C, O(patternCount): pi = w / siteCount, their sum, p = pi * patternCount / sum, the descending fill of
+   small / large, the pairing loop p[g] = p[g] + p[a] - 1, the leftovers set to 1 (alias 0).  It is built once per weight vector and
+   siteCount and kept until phyhip_set_pattern_weights is called; phyhip_get_support_alias_table returns it (prob [pattern], alias
+   [pattern], either may be NULL) so that a test can hold it.
+     THE DRAWS are not the reference's: its rand() stream is sequential and cannot be the device's (src/stats.c:4566-4572 takes two
+   rand() per draw).  They come from Philox4x32-10 (Salmon et al. 2011), counter-based and integer-only, so that an independent
+   restatement reproduces every draw bit for bit: key = (seed low word, seed high word), counter = (j, 0, r, 0) for draw pair j of
+   replicate r; draw 2j takes the output words (w0, w1), draw 2j+1 takes (w2, w3) -- dropped when siteCount is odd and 2j+1 ==
+   siteCount.  column = (w_a * patternCount) >> 32 (unlike (int)(len * r1) this can never index patternCount); the draw keeps the
+   column if w_b * 2^-32 < prob[column], else takes alias[column].  A replicate's draws depend on (seed, r, j) only -- not on
+   replicateCount, not on the launch geometry.  The support is therefore a Monte-Carlo estimate of the same probability as the
+   reference's, not the same number: two runs of the reference with different srand() differ the same way.
+     Numbers: one wave per replicate; lane l adds the draws of the pairs l, l + 64, .. in ascending order, the 64 partial sums meet
+   in a fixed butterfly (lane distance 32, 16, .., 1).  No floating-point atomics: the same bits from run to run, for any grid size
+   and any replicateCount.  Each sum lies within siteCount x 2^-52 x sum |terms| of the exact sum of its draws, each total within
+   patternCount x 2^-52 x sum |terms|.  Per draw the kernel gathers one 64-byte row {prob, the column's three values, its alias's
+   three values} of a table it rebuilds per call from the slots.
+     Nothing else changes: partials, scale vectors, matrices, the outputs of the last evaluation and the numerical warning stay what
+   they were, and no queued operation is executed.  The device work space (about 88 bytes per pattern and 32 per replicate) is
+   allocated or grown on use and kept; if it cannot be had: PHYHIP_ERROR_OUT_OF_MEMORY.
+     Sharded instance (one process): the slots live on the first shard's device -- a NULL snapshot copies each shard's pattern range
+   to its global offset there -- and the rest runs on that device; sharding changes no bit of the result.  Instances of
+   phyhip_comm_init_rank (a rank holds only its own patterns), PHYHIP_FLAG_CLASS_AXIS and PHYHIP_FLAG_GENERIC_LOOP instances:
+   PHYHIP_ERROR_NO_IMPLEMENTATION; mixture trees (the next_mixt loop of the reference) are not served.  slot outside 0..2,
+   siteCount <= 0, replicateCount <= 0, a slot never set, a negative weight, all weights zero (the reference exits at the last two):
+   PHYHIP_ERROR_OUT_OF_RANGE.  4 or 20 states are irrelevant here: one kernel. */
+int phyhip_calculate_sh_support(int instance, int siteCount, int replicateCount, unsigned long long seed,
+                                double *outSH, double *outRELL, double *outTotals,
+                                double *outReplicateSums, int *outAccepted);
+int phyhip_get_support_alias_table(int instance, int siteCount, double *outProb, int *outAlias);
+
 /* replaces beagleGetPartials, src/beagle_utils.c:252 (download hook for ancestral.c, cv.c, m4.c ...) */
 int phyhip_get_partials(int instance, int bufferIndex, int scaleIndex, double *outPartials);
 
@@ -463,6 +519,10 @@ int phyhip_profile_read_node_posteriors(int instance, double *outKernelMs, int *
    (shard sums and the per-pair sums included) and of the optimiser kernels (HIP events on the instance's stream; the host's
    starting values and the transfers excluded), and calls since the previous read; reading resets all three. */
 int phyhip_profile_read_pairwise(int instance, double *outCountMs, double *outOptimiseMs, int *outCalls);
+/* The kernels of phyhip_calculate_sh_support while the instance is being profiled (table, totals, draws, count): milliseconds (HIP
+   events on the instance's stream; the host's alias table and the transfers excluded) and calls since the previous read; reading
+   resets both. */
+int phyhip_profile_read_support(int instance, double *outKernelMs, int *outCalls);
 
 /* The resident evaluators (small nucleotide alignments, scalar wanted on the host): the launch-bound calls of a search --
    the chain of dLk calls of a branch-length optimisation (src/optimiz.c: Br_Len_Opt) and the short evaluations of SPR

@@ -101,6 +101,10 @@ typedef struct __Tree
      of this path.  The gate is mirrored, the bookkeeping stays the application's: its own function goes here. */
   short    do_alias_subpatt, update_alias_subpatt; /* tree->io->do_alias_subpatt, tree->update_alias_subpatt */
   void   (*alias_one_subpatt)(struct __Node *a, struct __Node *d, struct __Tree *tree);
+  int      init_len;          /* tree->data->init_len: sites of the alignment before compaction (Make_Tree_For_Lk sets the rounded
+                                 sum of the weights; a caller whose weights are not counts sets its own) */
+  unsigned long long sh_seed; /* seed of the draws of Statistics_To_SH / Statistics_to_RELL (the reference's are rand()'s; 0 at first; the
+                                 caller changes it per edge for independent draws) */
 } t_tree;
 
 #define PHL_N_SPARE 4
@@ -195,6 +199,19 @@ void Get_All_Ancestral_Probs(t_tree *tree, phydbl *probs);
    default).  dist: [n_otu][n_otu], symmetric, diagonal 0, at most DIST_MAX.  One category of rate 1, whatever the model's rate
    classes (ML_Dist forces this).  Fill_Missing_Dist and Bionj stay with the caller. */
 void ML_Dist(t_tree *tree, phydbl min_diff_lk_local, phydbl *dist);
+
+/* SH-like branch supports on the device (phyhip_calculate_sh_support; src/alrt.c).  aLRT() runs NNI_Neigh_BL per internal edge,
+   which evaluates the three NNI configurations with Lk(b) and keeps c_lnL_sorted of each (src/alrt.c:453,555,682):
+   Set_Log_Lks_aLRT(tree, k), k = 0..2, is that assignment -- log_lks_aLRT[k][site] = c_lnL_sorted[site] of the Lk(b) that has just
+   run -- as a device-to-device snapshot, no download.  Statistics_To_SH (src/alrt.c:1148-1298) and the deprecated Statistics_to_RELL
+   (src/alrt.c:1091-1140) then resample the three vectors: 10 000 replicates of tree->init_len sites under tree->wght, draws seeded by
+   tree->sh_seed (Philox4x32-10: not the reference's rand() stream, the same estimate).  tree->sh_seed is passed on UNCHANGED: two
+   calls with the same seed draw the same replicates, so a caller that wants every internal edge of a tree resampled independently
+   -- as the reference's running rand() stream does -- sets tree->sh_seed per edge (its run seed plus b->num, say) before the call.
+   Mixture trees are not served. */
+void   Set_Log_Lks_aLRT(t_tree *tree, int k);
+phydbl Statistics_To_SH(t_tree *tree);
+phydbl Statistics_to_RELL(t_tree *tree);
 
 void Set_Exit_Handler(void (*handler)(const char *msg));
 

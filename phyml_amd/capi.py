@@ -49,6 +49,7 @@ SYMBOLS = [
     "phyhip_calculate_class_mixture_eigen_lnl_dlnl", "phyhip_get_class_scale_factors", "phyhip_set_mixture_invariant_sites",
     "phyhip_calculate_edge_site_outputs_exact", "phyhip_calculate_node_state_posteriors", "phyhip_profile_read_node_posteriors",
     "phyhip_calculate_pairwise_ml_distances", "phyhip_set_pairwise_work_space", "phyhip_profile_read_pairwise",
+    "phyhip_set_support_site_log_likelihoods", "phyhip_calculate_sh_support", "phyhip_get_support_alias_table", "phyhip_profile_read_support",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -290,6 +291,45 @@ class Instance:
         a = C.c_double(0); b = C.c_double(0); n = C.c_int(0)
         _chk(self.L.phyhip_profile_read_pairwise(self.id, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
+
+    def set_support_site_lnl(self, slot, site_lnl=None):
+        """phyhip_set_support_site_log_likelihoods: slot 0..2 of the SH-like support's three per-pattern vectors (log_lks_aLRT);
+        site_lnl None: what the last edge evaluation left on the device, copied device to device."""
+        a = None if site_lnl is None else _f64(site_lnl)
+        assert a is None or a.size == self.P
+        fn = self.L.phyhip_set_support_site_log_likelihoods
+        fn.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        _chk(fn(self.id, int(slot), _ptr(a)))
+
+    def sh_support(self, site_count, replicates=10000, seed=0, want=()):
+        """phyhip_calculate_sh_support: (SH-like support, RELL support, totals c_0..c_2) of the three slots under the instance's
+        pattern weights (Statistics_To_SH / Statistics_to_RELL).  want: any of "sums" ([replicate][3], uncentred), "accepted"
+        ([replicate] 0 / 1); with a non-empty `want` the result is (sh, rell, totals, {name: array})."""
+        bad = set(want) - {"sums", "accepted"}
+        assert not bad, bad
+        sh = C.c_double(0); rell = C.c_double(0); tot = np.zeros(3)
+        extra = {}
+        if "sums" in want: extra["sums"] = np.zeros((int(replicates), 3))
+        if "accepted" in want: extra["accepted"] = np.zeros(int(replicates), np.int32)
+        fn = self.L.phyhip_calculate_sh_support
+        fn.argtypes = [C.c_int, C.c_int, C.c_int, C.c_ulonglong] + [C.c_void_p] * 5
+        _chk(fn(self.id, int(site_count), int(replicates), int(seed) & 0xFFFFFFFFFFFFFFFF, C.cast(C.byref(sh), C.c_void_p),
+                C.cast(C.byref(rell), C.c_void_p), _ptr(tot), _ptr(extra.get("sums")), _ptr(extra.get("accepted"))))
+        return (sh.value, rell.value, tot, extra) if want else (sh.value, rell.value, tot)
+
+    def support_alias_table(self, site_count):
+        """phyhip_get_support_alias_table: (prob, alias) of Sample_n_i_With_Proba_pi for the instance's weights and site_count"""
+        prob = np.zeros(self.P); alias = np.zeros(self.P, np.int32)
+        fn = self.L.phyhip_get_support_alias_table
+        fn.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _chk(fn(self.id, int(site_count), _ptr(prob), _ptr(alias)))
+        return prob, alias
+
+    def profile_read_support(self):
+        """(kernel ms, calls) of sh_support since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0)
+        _chk(self.L.phyhip_profile_read_support(self.id, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def get_partials(self, buf):
         out = np.zeros((self.P, self.C * self.S))

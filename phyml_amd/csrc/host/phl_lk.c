@@ -190,6 +190,12 @@ void Make_Tree_For_Lk_On_Devices(t_tree *tree, int n_pattern, const phydbl *wght
   tree->n_pattern = n_pattern;
   tree->wght      = (phydbl *)malloc(sizeof(phydbl) * n_pattern);
   memcpy(tree->wght, wght, sizeof(phydbl) * n_pattern);
+  if (tree->init_len <= 0)
+  { /* calign's init_len: the weights of a compacted alignment are its site counts */
+    phydbl sum = 0.0;
+    for (int i = 0; i < n_pattern; ++i) sum += wght[i];
+    tree->init_len = (int)(sum + 0.5);
+  }
   tree->invar = (short *)malloc(sizeof(short) * n_pattern);
   if (invar) memcpy(tree->invar, invar, sizeof(short) * n_pattern);
   else for (int i = 0; i < n_pattern; ++i) tree->invar[i] = -1;
@@ -824,4 +830,28 @@ void Get_All_Ancestral_Probs(t_tree *tree, phydbl *probs)
 void ML_Dist(t_tree *tree, phydbl min_diff_lk_local, phydbl *dist)
 {
   CHK(phyhip_calculate_pairwise_ml_distances(tree->b_inst, 0, 0, min_diff_lk_local, NULL, dist, NULL, NULL, NULL, NULL));
+}
+
+/* log_lks_aLRT[k][site] = c_lnL_sorted[site] (src/alrt.c:453,555,682) after an Lk(b): device to device */
+void Set_Log_Lks_aLRT(t_tree *tree, int k)
+{
+  CHK(phyhip_set_support_site_log_likelihoods(tree->b_inst, k, NULL));
+}
+
+#define SH_OCCURENCE 10000 /* src/alrt.c:1094,1151 */
+
+/* Statistics_To_SH (src/alrt.c:1148-1298) of the three snapshots, on the device */
+phydbl Statistics_To_SH(t_tree *tree)
+{
+  double res = 0.0;
+  CHKV(phyhip_calculate_sh_support(tree->b_inst, tree->init_len, SH_OCCURENCE, tree->sh_seed, &res, NULL, NULL, NULL, NULL), 0.0);
+  return res;
+}
+
+/* Statistics_to_RELL (src/alrt.c:1091-1140), deprecated in the reference: the same pass */
+phydbl Statistics_to_RELL(t_tree *tree)
+{
+  double res = 0.0;
+  CHKV(phyhip_calculate_sh_support(tree->b_inst, tree->init_len, SH_OCCURENCE, tree->sh_seed, NULL, &res, NULL, NULL, NULL), 0.0);
+  return res;
 }

@@ -97,7 +97,7 @@ static void release_instance(Instance *I)
   I->prof_spare.clear();
   void *ptrs[] = {I->d_partials, I->d_scales, I->d_tipcodes, I->d_masks, I->d_pmats, I->d_wght, I->d_invar, I->d_model,
                   I->d_site_lnl, I->d_site_lk, I->d_site_cat, I->d_fact, I->d_dot, I->d_block, I->d_result, I->d_warn, I->d_ops,
-                  I->d_pmscratch, I->d_afrag, I->d_tickets, I->d_mixexpl, I->d_dbg, I->d_tipmasks, I->d_tile_sums, I->d_big_tickets, I->d_big_stamps, I->d_big_recs, I->d_exact, I->d_anc, I->d_dist};
+                  I->d_pmscratch, I->d_afrag, I->d_tickets, I->d_mixexpl, I->d_dbg, I->d_tipmasks, I->d_tile_sums, I->d_big_tickets, I->d_big_stamps, I->d_big_recs, I->d_exact, I->d_anc, I->d_dist, I->d_sup_slots, I->d_sup_work};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (I->h_result) (void)hipHostFree(I->h_result);
@@ -614,6 +614,7 @@ int phyhip_set_pattern_weights(int instance, const double *w)
   int rc = flush_sync(I);
   if (rc) return rc;
   HIPCHK(hipMemcpy(I->d_wght, w, I->P * sizeof(double), hipMemcpyHostToDevice));
+  ++I->wght_epoch; // (the alias table of phyhip_calculate_sh_support is built per weight vector)
   return PHYHIP_SUCCESS;
 }
 

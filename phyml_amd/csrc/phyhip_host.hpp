@@ -11,6 +11,8 @@
 //   phyhip_exact.hip     the per-pattern outputs of an edge as the reference's doubles (a kernel and an entry point of its own)
 //   phyhip_ancestral.hip the marginal state posteriors of internal nodes (a kernel and an entry point of its own)
 //   phyhip_dist.hip      the pairwise ML distance matrix, ML_Dist (count, sums and optimiser kernels, an entry point of its own)
+//   phyhip_support.hip   the resampling behind SH-like branch supports, Statistics_To_SH (table, totals, draw and count kernels,
+//                        entry points of its own)
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
@@ -225,6 +227,19 @@ struct Instance
   size_t    dist_band_bytes = kDistBandBytes; // ... and the bound on the raw counts held at a time (phyhip_set_pairwise_work_space)
   double    dist_prof_count_ms = 0.0, dist_prof_opt_ms = 0.0; // while profiling: its count / optimise kernels (phyhip_profile_read_pairwise)
   int       dist_prof_n = 0;
+  // phyhip_calculate_sh_support (phyhip_support.hip); all of it lives on the first shard of a sharded instance
+  void     *d_sup_slots = nullptr; // the three per-pattern vectors log_lks_aLRT[0..2], [3][P of the whole instance]: allocated on first use, kept
+  bool      sup_slot_set[3] = {false, false, false};
+  void     *d_sup_work = nullptr;  // weights, alias table, gather table, sums and flags: grown on use, kept
+  size_t    sup_work_cap = 0;
+  unsigned long long wght_epoch = 0, sup_epoch = 0; // phyhip_set_pattern_weights calls so far; their sum over the shards when the alias table was built
+  int       sup_sites = 0;         // ... and the site count it was built for
+  bool      sup_alias_valid = false, sup_table_on_device = false; // the host's table is current; d_sup_work holds it
+  long long sup_dev_P = 0;
+  std::vector<double> sup_w, sup_prob; // the weights the table was built from (all shards) and Sample_n_i_With_Proba_pi's prob
+  std::vector<int>    sup_alias;       // ... and alias
+  double    sup_prof_ms = 0.0;     // while profiling: its kernels (phyhip_profile_read_support)
+  int       sup_prof_n = 0;
   double   *d_block    = nullptr; // [2][grid]
   double   *d_result   = nullptr; // [2]
   double   *h_result   = nullptr; // pinned, device-visible: [0..1] results, [2] sequence number (as u64)

@@ -50,7 +50,7 @@ class t_tree(C.Structure):
                 ("host_pmat", C.c_short), ("c_lnL", C.c_double), ("old_lnL", C.c_double), ("c_dlnL", C.c_double),
                 ("n_edges_traversed", C.c_int), ("spare_p_lk_idx", C.c_int), ("spare_Pij_idx", C.c_int),
                 ("e_root", C.POINTER(t_edge)), ("do_alias_subpatt", C.c_short), ("update_alias_subpatt", C.c_short),
-                ("alias_one_subpatt", C.c_void_p)]
+                ("alias_one_subpatt", C.c_void_p), ("init_len", C.c_int), ("sh_seed", C.c_ulonglong)]
 
 
 _lib = None
@@ -71,7 +71,7 @@ def load():
         L = C.CDLL(LK_LIB_PATH)
         L.Make_Tree_From_Edges.restype = C.POINTER(t_tree)
         L.Make_Model_Basic.restype = C.POINTER(t_mod)
-        for f in ("Lk", "dLk", "Br_Len_Newton", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk"):
+        for f in ("Lk", "dLk", "Br_Len_Newton", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk", "Statistics_To_SH", "Statistics_to_RELL"):
             getattr(L, f).restype = C.c_double
         # tests must survive the reference's print-and-Exit() convention
         L.Set_Exit_Handler(_exit_handler)
@@ -228,6 +228,25 @@ class LkTree:
         self.L.ML_Dist(self.tree, C.c_double(min_diff_lk_local), _dp(out))
         _raise_if_error()
         return out
+
+    def Set_Log_Lks_aLRT(self, k):
+        """log_lks_aLRT[k] = c_lnL_sorted of the Lk(b) that has just run, kept on the device (k = 0..2)"""
+        self.L.Set_Log_Lks_aLRT(self.tree, int(k)); _raise_if_error()
+
+    def Statistics_To_SH(self, init_len=None, seed=None):
+        """Statistics_To_SH: the SH-like support from the three snapshots, 10 000 replicates of init_len sites on the device
+        (init_len / seed: tree->init_len / tree->sh_seed are set first when given)"""
+        if init_len is not None: self.tree.contents.init_len = int(init_len)
+        if seed is not None: self.tree.contents.sh_seed = int(seed)
+        v = self.L.Statistics_To_SH(self.tree); _raise_if_error()
+        return v
+
+    def Statistics_to_RELL(self, init_len=None, seed=None):
+        """Statistics_to_RELL (deprecated in the reference): the RELL support from the same pass"""
+        if init_len is not None: self.tree.contents.init_len = int(init_len)
+        if seed is not None: self.tree.contents.sh_seed = int(seed)
+        v = self.L.Statistics_to_RELL(self.tree); _raise_if_error()
+        return v
 
     def dLk(self, l, b):
         lv = C.c_double(l)
