@@ -61,6 +61,18 @@ def synthetic_pair(n_otu, P, ns, C, seed, lmin=0.02, lmax=0.3, wght=None, apply_
     t.set_tips(tip_partials=tv)
     return t, ot, tree, st
 
+
+def device_compute_units(device=None):
+    """phyhip_instance_details::computeUnits of the device a tree is made on.  The C host layer keeps the details of the instance
+    it creates to itself (t.inst.details is None), so a throw-away instance of the same device reports them."""
+    from phyml_amd import capi
+    inst = capi.Instance(4, 10, 4, 16, 5, 4, device=device)
+    try:
+        return int(inst.details.computeUnits)
+    finally:
+        inst.close()
+
+
 def assert_device_state_is_the_oracles(t, ot, buffer_of=None, what=None):
     """What a call sequence left in device memory against the oracle tree that followed it: every transition matrix of the tree
     and every partial vector and scale vector of the tree's own buffers, bit for bit (patterns of weight zero excepted, as
