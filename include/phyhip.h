@@ -562,6 +562,42 @@ int phyhip_set_virtual_buffers(int instance, int minOperations);
    re-issues in front of readers, out[3] storing re-issues (materialisations).  Sharded instances: the first shard's counters. */
 int phyhip_get_virtual_stats(int instance, long long out[4]);
 
+/* ---- parsimony (src/pars.c) --------------------------------------------------------------------------------------------------- */
+
+/* Update_Partial_Pars (src/pars.c:239-393) and Pars / Pars_Core (src/pars.c:20-52, 397-437) on the device, in the reference's own
+   integers: every value that leaves through these calls equals t_edge::ui_l/r, pars_l/r, p_pars_l/r, tree->site_pars, tree->c_pars.
+   Parsimony buffers share the index space of the partials buffers: k < tipCount is tip k -- read from the tip data the instance
+   already holds (the reference's Init_Ui_Tips / Init_Partial_Pars_Tips run the likelihood's character encoders), so a tip rewrite
+   is seen in stream order -- and k >= tipCount is the parsimony plane that goes with partials buffer k.  Planes exist once
+   phyhip_set_parsimony was called, and only for the mode in use: Fitch (general == 0: {ui, pars}, 8 bytes per pattern and buffer)
+   or the step matrix (general != 0: stateCount ints per pattern and buffer).
+   The parsimony queue is its own: none of these calls launches a queued likelihood operation, writes partials, scale vectors,
+   matrices, site outputs or the warning flag, or counts as a step for the resident evaluators.  4 and 20 states.  Sharded
+   instances of one process: every shard runs its pattern range, the host adds the 64-bit sums, per-pattern downloads are
+   concatenated.  Not built (PHYHIP_ERROR_NO_IMPLEMENTATION): ranks of phyhip_comm_init_rank, class-axis instances, mixture trees
+   (MIXT_Pars).  Every check happens before any device work: a call before phyhip_set_parsimony PHYHIP_ERROR_UNINITIALIZED_INSTANCE;
+   a buffer index out of range, a destination that is a tip or one of its own children PHYHIP_ERROR_OUT_OF_RANGE. */
+typedef struct { int destination, child1, child2; } phyhip_parsimony_operation;
+
+/* enable parsimony; general != 0 needs stepMatrix[S*S] (row = parent state: tree->step_mat of Get_Step_Mat, the caller's own), else it
+   may be NULL; re-callable (what is queued runs first in the mode it was queued in; a mode switch frees the other mode's planes) */
+int phyhip_set_parsimony(int instance, int general, const int *stepMatrix);
+/* queue operations (no launch); executed in order by the next calculate/get/synchronize, or when the staging list is full */
+int phyhip_update_partial_parsimony(int instance, const phyhip_parsimony_operation *ops, int count);
+/* flush the queue and score the edge whose two sides are these buffers (either may be a tip) in the SAME launch; count may have been
+   0.  *outParsimony = sum over patterns of site_pars * weight, exact in 64 bits; a weight that is not an integer:
+   PHYHIP_ERROR_NO_IMPLEMENTATION and nothing runs (the reference's c_pars += site_pars * wght truncates a double into an int at
+   every pattern, in order).  outParsimony == NULL: the queue and the per-pattern scores only, whatever the weights -- the caller
+   forms its own sum from phyhip_get_site_parsimony. */
+int phyhip_calculate_edge_parsimony(int instance, int buffer1, int buffer2, long long *outParsimony);
+int phyhip_get_site_parsimony(int instance, int *outSitePars);                       /* of the last scored edge */
+/* flushes the queue; Fitch mode fills outUi / outPars [pattern], the step-matrix mode outPPars [pattern][state]; any may be NULL, one
+   the mode does not hold PHYHIP_ERROR_OUT_OF_RANGE */
+int phyhip_get_partial_parsimony(int instance, int bufferIndex, int *outUi, int *outPars, int *outPPars /* [pattern][state] */);
+/* while phyhip_profile(instance, 1): milliseconds of the parsimony kernels (HIP events on the instance's stream), their launches and
+   pattern x (operations + scored edges) since the previous read; reading resets all three.  Sharded: the slowest shard's time. */
+int phyhip_profile_read_parsimony(int instance, double *outKernelMs, int *outLaunches, double *outPatternUpdates);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,13 @@ typedef struct __Tree
                                  sum of the weights; a caller whose weights are not counts sets its own) */
   unsigned long long sh_seed; /* seed of the draws of Statistics_To_SH / Statistics_to_RELL (the reference's are rand()'s; 0 at first; the
                                  caller changes it per edge for independent draws) */
+  /* parsimony (src/pars.c; Make_Tree_For_Pars): appended, every offset above stays what it was */
+  int      c_pars, best_pars; /* tree->c_pars, tree->best_pars */
+  int     *site_pars;         /* tree->site_pars [n_pattern], filled by Pars */
+  short    general_pars;      /* mod->s_opt->general_pars (`phyml --pars`): the step matrix instead of Fitch's sets */
+  int     *step_mat;          /* tree->step_mat [ns][ns], row = parent state: Get_Step_Mat's for 4 states and 0/1 otherwise, or the caller's
+                                 own, set before Make_Tree_For_Pars (amino acids: the reference's table is PhyML's to pass in) */
+  short    own_step_mat;      /* step_mat was allocated by Get_Step_Mat (Free_Tree_Pars frees it) */
 } t_tree;
 
 #define PHL_N_SPARE 4
@@ -212,6 +219,37 @@ void ML_Dist(t_tree *tree, phydbl min_diff_lk_local, phydbl *dist);
 void   Set_Log_Lks_aLRT(t_tree *tree, int k);
 phydbl Statistics_To_SH(t_tree *tree);
 phydbl Statistics_to_RELL(t_tree *tree);
+
+/* ---- parsimony: src/pars.h on the device (phyhip_set_parsimony ...) ---------------------------------------------------------------
+   For a tree made with Make_Tree_For_Lk whose tips are loaded: the parsimony buffers are the partials buffers' indices (Prune_Subtree /
+   Graft_Subtree swap ui_*, pars_* and p_pars_* together with p_lk_*, src/utilities.c:6269-6278), tips are read from the tip data
+   the instance holds.  Names and semantics are the reference's:
+     Make_Tree_For_Pars(tree)            src/make.c      tree->site_pars, Get_Step_Mat, parsimony enabled on the instance in the mode
+                                                         tree->general_pars says (call it again after changing general_pars)
+     Pars(b,tree)                        src/pars.c:20   b == NULL: Post_Order_Pars from a_nodes[0] (+ Pre_Order_Pars with both_sides), then
+                                                         a_nodes[0]->b[0] is scored, all in ONE device call; fills tree->site_pars, tree->c_pars
+     Update_Partial_Pars(tree,b,n)       src/pars.c:239  one operation queued (children by neighbour position, as Update_Partial_Lk);
+                                                         returns at once for a tip, after the alias gate
+     Post_Order_Pars / Pre_Order_Pars    src/pars.c:56/77
+     Pars_At_Given_Edge(b,tree)          src/pars.c:468
+     Update_Pars_At_Given_Edge(b,tree)   src/pars.c:488
+     Get_Step_Mat(tree)                  src/pars.c:498  nucleotides (transition 1, transversion 2, ACGT order) and the 0/1 matrix only; a
+                                                         step_mat the caller has set is left alone
+   c_pars: weights that are whole numbers give the exact sum (as the reference's int holds it); any other weight makes the device
+   refuse the sum, and Pars runs the reference's truncating loop c_pars += site_pars * wght itself over the downloaded site_pars.
+   Not built: rooted trees (tree->e_root) and mixture trees exit with "not built". */
+void Make_Tree_For_Pars(t_tree *tree);
+void Free_Tree_Pars(t_tree *tree);
+int  Pars(t_edge *b, t_tree *tree);
+void Update_Partial_Pars(t_tree *tree, t_edge *b_fcus, t_node *n);
+void Post_Order_Pars(t_node *a, t_node *d, t_tree *tree);
+void Pre_Order_Pars(t_node *a, t_node *d, t_tree *tree);
+int  Pars_At_Given_Edge(t_edge *b, t_tree *tree);
+int  Update_Pars_At_Given_Edge(t_edge *b_fcus, t_tree *tree);
+void Get_Step_Mat(t_tree *tree);
+/* download hooks: the side of b at node d -- ui / pars [n_pattern] (Fitch) or p_pars [n_pattern][ns] (step matrix); NULL: not wanted */
+void Get_Partial_Pars(t_tree *tree, t_edge *b, t_node *d, int *ui, int *pars, int *p_pars);
+void Get_Site_Pars(t_tree *tree, int *site_pars);
 
 void Set_Exit_Handler(void (*handler)(const char *msg));
 

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libphyhip.so")
 
 
 class PhyhipError(RuntimeError):
-    pass
+    code = None  # the PHYHIP_ERROR_* value, where a C entry point returned one
 
 
 class Operation(C.Structure):
@@ -50,11 +50,17 @@ SYMBOLS = [
     "phyhip_calculate_edge_site_outputs_exact", "phyhip_calculate_node_state_posteriors", "phyhip_profile_read_node_posteriors",
     "phyhip_calculate_pairwise_ml_distances", "phyhip_set_pairwise_work_space", "phyhip_profile_read_pairwise",
     "phyhip_set_support_site_log_likelihoods", "phyhip_calculate_sh_support", "phyhip_get_support_alias_table", "phyhip_profile_read_support",
+    "phyhip_set_parsimony", "phyhip_update_partial_parsimony", "phyhip_calculate_edge_parsimony", "phyhip_get_site_parsimony",
+    "phyhip_get_partial_parsimony", "phyhip_profile_read_parsimony",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
 FLAG_CLASS_AXIS = 1 << 41  # PHYHIP_FLAG_CLASS_AXIS
 UNIQUE_ID_BYTES = 128
+PARS_TILE = 256  # kParsTile of phyml_amd/csrc/phyhip_pars.hip: patterns per workgroup of the parsimony kernels
+PARS_STAGING = 4096  # kParsStaging: operations one parsimony launch takes (a longer queue is launched as it fills)
+MAX_PARS = 1000000000  # src/utilities.h
+ERROR_UNINITIALIZED_INSTANCE, ERROR_OUT_OF_RANGE, ERROR_NO_IMPLEMENTATION = -4, -5, -7
 
 _lib = None
 
@@ -79,7 +85,9 @@ def load():
 
 def _chk(rc):
     if rc < 0:
-        raise PhyhipError(f"phyhip error {rc}: {load().phyhip_get_last_error().decode()}")
+        e = PhyhipError(f"phyhip error {rc}: {load().phyhip_get_last_error().decode()}")
+        e.code = rc
+        raise e
     return rc
 
 
@@ -330,6 +338,46 @@ class Instance:
         ms = C.c_double(0); n = C.c_int(0)
         _chk(self.L.phyhip_profile_read_support(self.id, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    # -- parsimony (src/pars.c)
+    def set_parsimony(self, general=False, step_matrix=None):
+        """phyhip_set_parsimony: Fitch mode, or -- general -- the step-matrix mode with step_matrix [S][S] (row = parent state)"""
+        m = None if step_matrix is None else np.ascontiguousarray(step_matrix, dtype=np.int32)
+        assert m is None or m.size == self.S * self.S
+        _chk(self.L.phyhip_set_parsimony(self.id, 1 if general else 0, _ptr(m)))
+
+    def update_partial_parsimony(self, ops):
+        """phyhip_update_partial_parsimony: ops = iterable of (dest, child1, child2), queued"""
+        a = np.ascontiguousarray(np.array(list(ops), dtype=np.int32).reshape(-1, 3))
+        _chk(self.L.phyhip_update_partial_parsimony(self.id, _ptr(a), int(a.shape[0])))
+
+    def edge_parsimony(self, buffer1, buffer2, with_sum=True):
+        """phyhip_calculate_edge_parsimony: the queue, then the score of the edge (buffer1, buffer2): the 64-bit weighted sum, or
+        None with with_sum=False (per-pattern scores only)"""
+        out = C.c_longlong(0)
+        _chk(self.L.phyhip_calculate_edge_parsimony(self.id, int(buffer1), int(buffer2), C.byref(out) if with_sum else None))
+        return out.value if with_sum else None
+
+    def site_parsimony(self):
+        out = np.zeros(self.P, np.int32)
+        _chk(self.L.phyhip_get_site_parsimony(self.id, _ptr(out)))
+        return out
+
+    def partial_parsimony(self, buf, general=False):
+        """phyhip_get_partial_parsimony: (ui, pars) of the buffer, or -- general -- p_pars [pattern][state]"""
+        if general:
+            pp = np.zeros((self.P, self.S), np.int32)
+            _chk(self.L.phyhip_get_partial_parsimony(self.id, int(buf), None, None, _ptr(pp)))
+            return pp
+        ui = np.zeros(self.P, np.int32); pars = np.zeros(self.P, np.int32)
+        _chk(self.L.phyhip_get_partial_parsimony(self.id, int(buf), _ptr(ui), _ptr(pars), None))
+        return ui, pars
+
+    def profile_read_parsimony(self):
+        """(kernel ms, launches, pattern updates) of the parsimony kernels since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0); u = C.c_double(0)
+        _chk(self.L.phyhip_profile_read_parsimony(self.id, C.byref(ms), C.byref(n), C.byref(u)))
+        return ms.value, n.value, u.value
 
     def get_partials(self, buf):
         out = np.zeros((self.P, self.C * self.S))

@@ -158,6 +158,7 @@ void Free_Tree(t_tree *tree)
     free(tree->a_edges[e]);
   }
   free(tree->a_nodes); free(tree->a_edges); free(tree->wght); free(tree->invar);
+  Free_Tree_Pars(tree);
   free(tree);
 }
 
@@ -854,4 +855,192 @@ phydbl Statistics_to_RELL(t_tree *tree)
   double res = 0.0;
   CHKV(phyhip_calculate_sh_support(tree->b_inst, tree->init_len, SH_OCCURENCE, tree->sh_seed, NULL, &res, NULL, NULL, NULL), 0.0);
   return res;
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* parsimony (src/pars.c)                                                                             */
+/* ------------------------------------------------------------------------------------------------ */
+
+void Get_Step_Mat(t_tree *tree)
+{ /* src/pars.c:498: nucleotides -- transition 1, transversion 2, states in ACGT order -- and the 0/1 matrix for everything else */
+  if (tree->step_mat) return;
+  const int ns = tree->mod->ns;
+  tree->step_mat = (int *)calloc((size_t)ns * ns, sizeof(int));
+  tree->own_step_mat = YES;
+  for (int i = 0; i < ns; ++i)
+    for (int j = 0; j < ns; ++j)
+    {
+      if (i == j) continue;
+      /* A <-> G (0, 2) and C <-> T (1, 3) are the transitions */
+      tree->step_mat[i * ns + j] = (ns == 4 && ((i ^ j) != 2)) ? 2 : 1;
+    }
+}
+
+void Make_Tree_For_Pars(t_tree *tree)
+{
+  if (tree->b_inst < 0) { Lk_Exit("Make_Tree_For_Pars", "the device instance does not exist (Make_Tree_For_Lk first)"); return; }
+  if (tree->e_root) { Lk_Exit("Make_Tree_For_Pars", "rooted trees are not built"); return; }
+  if (!tree->site_pars) tree->site_pars = (int *)calloc((size_t)tree->n_pattern, sizeof(int));
+  Get_Step_Mat(tree);
+  CHK(phyhip_set_parsimony(tree->b_inst, tree->general_pars ? 1 : 0, tree->step_mat));
+}
+
+void Free_Tree_Pars(t_tree *tree)
+{
+  free(tree->site_pars);
+  tree->site_pars = NULL;
+  if (tree->own_step_mat) free(tree->step_mat);
+  tree->step_mat = NULL;
+  tree->own_step_mat = NO;
+}
+
+/* destination and children of the side of b_fcus at n: the l_v1 / l_v2 / r_v1 / r_v2 resolution of src/pars.c:279-352 over neighbour
+   positions, as Fill_Operation does it for the partials (the same buffer indices) */
+static int Partial_Pars_Operation(t_tree *tree, t_edge *b_fcus, t_node *n, phyhip_parsimony_operation *op)
+{
+  if (tree->do_alias_subpatt == YES && tree->update_alias_subpatt == YES && tree->alias_one_subpatt) /* src/pars.c:268-270 */
+    tree->alias_one_subpatt((n == b_fcus->left) ? b_fcus->rght : b_fcus->left, n, tree);
+  if (n->tax) return 0;                                                                              /* :272 */
+  phyhip_operation f;
+  if (Fill_Operation(b_fcus, n, &f) < 0) { Lk_Exit("Update_Partial_Pars", "node is not an internal node of degree 3"); return 0; }
+  op->destination = f.destinationPartials;
+  op->child1      = f.child1Partials;
+  op->child2      = f.child2Partials;
+  return 1;
+}
+
+void Update_Partial_Pars(t_tree *tree, t_edge *b_fcus, t_node *n)
+{
+  phyhip_parsimony_operation op;
+  if (tree->e_root) { Lk_Exit("Update_Partial_Pars", "rooted trees are not built"); return; }
+  if (!Partial_Pars_Operation(tree, b_fcus, n, &op)) return;
+  CHK(phyhip_update_partial_parsimony(tree->b_inst, &op, 1));
+}
+
+typedef struct { phyhip_parsimony_operation *ops; int n, cap; } pars_batch;
+static void Batch_Partial_Pars(pars_batch *q, t_tree *tree, t_edge *b, t_node *d)
+{
+  if (q->n == q->cap)
+  {
+    q->cap = q->cap ? 2 * q->cap : 256;
+    q->ops = (phyhip_parsimony_operation *)realloc(q->ops, sizeof(phyhip_parsimony_operation) * (size_t)q->cap);
+  }
+  if (Partial_Pars_Operation(tree, b, d, &q->ops[q->n])) q->n++;
+}
+static void Batch_Submit_Pars(pars_batch *q, t_tree *tree)
+{
+  const int rc = q->n > 0 ? phyhip_update_partial_parsimony(tree->b_inst, q->ops, q->n) : 0;
+  free(q->ops);
+  q->ops = NULL; q->n = q->cap = 0;
+  if (rc < 0) Lk_Exit("phyhip_update_partial_parsimony", phyhip_get_last_error());
+}
+
+/* the recursions of src/pars.c:56-93, iterative (as Post_Order_Lk / Pre_Order_Lk), their operations handed over in one call each */
+void Post_Order_Pars(t_node *a, t_node *d, t_tree *tree)
+{
+  typedef struct { t_node *a, *d; int i, dir; } frame;
+  frame *st = (frame *)malloc(sizeof(frame) * (size_t)(2 * tree->n_otu));
+  int    sp = 0;
+  pars_batch q = {NULL, 0, 0};
+  st[sp++]  = (frame){a, d, 0, -1};
+  while (sp > 0)
+  {
+    frame *f = &st[sp - 1];
+    if (f->d->tax) { --sp; continue; }
+    if (f->i < 3)
+    {
+      const int i = f->i++;
+      if (f->d->v[i] != f->a) st[sp++] = (frame){f->d, f->d->v[i], 0, -1};
+      else f->dir = i;
+      continue;
+    }
+    if (f->dir < 0) { free(st); free(q.ops); Lk_Exit("Post_Order_Pars", "direction towards the ancestor not found"); return; }
+    Batch_Partial_Pars(&q, tree, f->d->b[f->dir], f->d);
+    --sp;
+  }
+  free(st);
+  Batch_Submit_Pars(&q, tree);
+}
+
+void Pre_Order_Pars(t_node *a, t_node *d, t_tree *tree)
+{
+  typedef struct { t_node *a, *d; int i; } frame;
+  frame *st = (frame *)malloc(sizeof(frame) * (size_t)(2 * tree->n_otu));
+  int    sp = 0;
+  pars_batch q = {NULL, 0, 0};
+  st[sp++]  = (frame){a, d, 0};
+  while (sp > 0)
+  {
+    frame *f = &st[sp - 1];
+    if (f->d->tax || f->i == 3) { --sp; continue; }
+    const int i = f->i++;
+    if (f->d->v[i] != f->a)
+    {
+      Batch_Partial_Pars(&q, tree, f->d->b[i], f->d);
+      st[sp++] = (frame){f->d, f->d->v[i], 0};
+    }
+  }
+  free(st);
+  Batch_Submit_Pars(&q, tree);
+}
+
+/* the site loop of Pars / Pars_At_Given_Edge (src/pars.c:41-51, :475-483) for edge b: what is queued and the score in one device call */
+static int Pars_Score(t_edge *b, t_tree *tree)
+{
+  const int left = b->left->tax ? b->left->num : b->p_lk_left_idx;
+  const int rght = b->rght->tax ? b->p_lk_tip_idx : b->p_lk_rght_idx;
+  long long sum  = 0;
+  if (!tree->site_pars) { Lk_Exit("Pars", "Make_Tree_For_Pars was not called"); return 0; }
+  int rc = phyhip_calculate_edge_parsimony(tree->b_inst, left, rght, &sum);
+  if (rc == PHYHIP_ERROR_NO_IMPLEMENTATION)
+  { /* a weight that is not a whole number: the reference's own loop, its int truncated at every pattern, over the device's site_pars */
+    rc = phyhip_calculate_edge_parsimony(tree->b_inst, left, rght, NULL);
+    if (rc >= 0) rc = phyhip_get_site_parsimony(tree->b_inst, tree->site_pars);
+    if (rc < 0) { Lk_Exit("phyhip_calculate_edge_parsimony", phyhip_get_last_error()); return 0; }
+    tree->c_pars = 0;
+    for (int site = 0; site < tree->n_pattern; ++site) tree->c_pars += tree->site_pars[site] * tree->wght[site];
+    return tree->c_pars;
+  }
+  if (rc < 0) { Lk_Exit("phyhip_calculate_edge_parsimony", phyhip_get_last_error()); return 0; }
+  CHKV(phyhip_get_site_parsimony(tree->b_inst, tree->site_pars), 0);
+  tree->c_pars = (int)sum;
+  return tree->c_pars;
+}
+
+int Pars(t_edge *b, t_tree *tree)
+{
+  if (tree->e_root) { Lk_Exit("Pars", "rooted trees are not built"); return 0; }
+  if (b == NULL)
+  { /* src/pars.c:33-39 */
+    Post_Order_Pars(tree->a_nodes[0], tree->a_nodes[0]->v[0], tree);
+    if (tree->both_sides == YES) Pre_Order_Pars(tree->a_nodes[0], tree->a_nodes[0]->v[0], tree);
+    b = tree->a_nodes[0]->b[0];
+  }
+  return Pars_Score(b, tree);
+}
+
+int Pars_At_Given_Edge(t_edge *b, t_tree *tree)
+{
+  if (tree->e_root) { Lk_Exit("Pars_At_Given_Edge", "rooted trees are not built"); return 0; }
+  return Pars_Score(b, tree);
+}
+
+int Update_Pars_At_Given_Edge(t_edge *b_fcus, t_tree *tree)
+{ /* src/pars.c:488-494: two queued operations + the score = one launch */
+  Update_Partial_Pars(tree, b_fcus, b_fcus->left);
+  Update_Partial_Pars(tree, b_fcus, b_fcus->rght);
+  tree->c_pars = Pars(b_fcus, tree);
+  return tree->c_pars;
+}
+
+void Get_Partial_Pars(t_tree *tree, t_edge *b, t_node *d, int *ui, int *pars, int *p_pars)
+{
+  const int idx = (d == b->left) ? b->p_lk_left_idx : b->p_lk_rght_idx;
+  if (d->tax) { Lk_Exit("Get_Partial_Pars", "tips hold no parsimony plane"); return; }
+  CHK(phyhip_get_partial_parsimony(tree->b_inst, idx, ui, pars, p_pars));
+}
+
+void Get_Site_Pars(t_tree *tree, int *site_pars)
+{
+  CHK(phyhip_get_site_parsimony(tree->b_inst, site_pars));
 }

@@ -95,6 +95,7 @@ static void release_instance(Instance *I)
   if (I->stream) (void)hipStreamSynchronize(I->stream);
   for (hipEvent_t e : I->prof_spare) (void)hipEventDestroy(e);
   I->prof_spare.clear();
+  pars_release(I);
   void *ptrs[] = {I->d_partials, I->d_scales, I->d_tipcodes, I->d_masks, I->d_pmats, I->d_wght, I->d_invar, I->d_model,
                   I->d_site_lnl, I->d_site_lk, I->d_site_cat, I->d_fact, I->d_dot, I->d_block, I->d_result, I->d_warn, I->d_ops,
                   I->d_pmscratch, I->d_afrag, I->d_tickets, I->d_mixexpl, I->d_dbg, I->d_tipmasks, I->d_tile_sums, I->d_big_tickets, I->d_big_stamps, I->d_big_recs, I->d_exact, I->d_anc, I->d_dist, I->d_sup_slots, I->d_sup_work};
@@ -1187,7 +1188,8 @@ int phyhip_synchronize(int instance)
 {
   if (Group *G = get_group(instance)) return group_each(G, [&](int id, long long, long long) { return phyhip_synchronize(id); });
   GET_INST(I, instance);
-  const int rc = flush_sync(I);
+  int rc = pars_flush_queue(I);
+  if (rc == 0) rc = flush_sync(I);
   if (rc == 0) { I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch; } // nothing queued is left
   return rc;
 }

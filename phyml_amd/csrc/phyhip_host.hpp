@@ -13,6 +13,7 @@
 //   phyhip_dist.hip      the pairwise ML distance matrix, ML_Dist (count, sums and optimiser kernels, an entry point of its own)
 //   phyhip_support.hip   the resampling behind SH-like branch supports, Statistics_To_SH (table, totals, draw and count kernels,
 //                        entry points of its own)
+//   phyhip_pars.hip      parsimony scores, Update_Partial_Pars / Pars (Fitch and step-matrix kernels, a queue and entry points of its own)
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
@@ -143,6 +144,7 @@ struct StagingRing
 };
 
 struct Collective;
+struct ParsState;
 
 constexpr int kPushCmdsDefault = 3;    // uncached device memory (see Instance::push_cmds; measured against 1 / 2 / host memory, profiles/r04_latency.md)
 constexpr int kResidentDirect = 16;    // up to this many resident workgroups poll the host themselves, above that workgroup 0 relays (measured: 8 / 16 / 32, docs/history/tools/gpu_direct_ab.sh)
@@ -240,6 +242,7 @@ struct Instance
   std::vector<int>    sup_alias;       // ... and alias
   double    sup_prof_ms = 0.0;     // while profiling: its kernels (phyhip_profile_read_support)
   int       sup_prof_n = 0;
+  struct ParsState *pars = nullptr; // phyhip_set_parsimony (phyhip_pars.hip): planes, queue and work space of the parsimony calls
   double   *d_block    = nullptr; // [2][grid]
   double   *d_result   = nullptr; // [2]
   double   *h_result   = nullptr; // pinned, device-visible: [0..1] results, [2] sequence number (as u64)
@@ -611,6 +614,10 @@ static double ns_since(const struct timespec &t0)
   clock_gettime(CLOCK_MONOTONIC, &t1);
   return (double)(t1.tv_sec - t0.tv_sec) * 1e9 + (double)(t1.tv_nsec - t0.tv_nsec);
 }
+
+// ---- phyhip_pars.hip -----------------------------------------------------------------------------------------------------
+void pars_release(Instance *I);     // phyhip_finalize_instance
+int  pars_flush_queue(Instance *I); // phyhip_synchronize: the queued parsimony operations run too
 
 // ---- phyhip_resident.hip -------------------------------------------------------------------------------------------------
 void       resident_stop(Resident &R);

@@ -53,6 +53,13 @@ class t_tree(C.Structure):
                 ("alias_one_subpatt", C.c_void_p), ("init_len", C.c_int), ("sh_seed", C.c_ulonglong)]
 
 
+class t_tree_pars(t_tree):
+    """t_tree with the parsimony fields the C struct has appended behind sh_seed (a ctypes subclass lays its fields out behind the
+    base's): what the host layer's trees are"""
+    _fields_ = [("c_pars", C.c_int), ("best_pars", C.c_int), ("site_pars", C.POINTER(C.c_int)), ("general_pars", C.c_short),
+                ("step_mat", C.POINTER(C.c_int)), ("own_step_mat", C.c_short)]
+
+
 _lib = None
 _errors = []
 
@@ -69,7 +76,7 @@ def load():
         if not os.path.exists(LK_LIB_PATH):
             raise capi.PhyhipError(f"{LK_LIB_PATH} not built: run __graft_entry__.build()")
         L = C.CDLL(LK_LIB_PATH)
-        L.Make_Tree_From_Edges.restype = C.POINTER(t_tree)
+        L.Make_Tree_From_Edges.restype = C.POINTER(t_tree_pars)
         L.Make_Model_Basic.restype = C.POINTER(t_mod)
         for f in ("Lk", "dLk", "Br_Len_Newton", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk", "Statistics_To_SH", "Statistics_to_RELL"):
             getattr(L, f).restype = C.c_double
@@ -247,6 +254,55 @@ class LkTree:
         if seed is not None: self.tree.contents.sh_seed = int(seed)
         v = self.L.Statistics_to_RELL(self.tree); _raise_if_error()
         return v
+
+    # --- parsimony (same names as src/pars.h) ----------------------------------------------------------------
+    def Make_Tree_For_Pars(self, general_pars=False, step_mat=None):
+        """Make_Tree_For_Pars after tree->general_pars (and, given, the caller's own tree->step_mat [ns][ns]) are set; re-callable"""
+        t = self.tree.contents
+        t.general_pars = 1 if general_pars else 0
+        if step_mat is not None:
+            if t.own_step_mat:
+                self.L.Free_Tree_Pars(self.tree)
+            self._step_mat = np.ascontiguousarray(step_mat, dtype=np.int32); assert self._step_mat.size == self.S * self.S
+            t.step_mat = self._step_mat.ctypes.data_as(C.POINTER(C.c_int))
+            t.own_step_mat = 0
+        self.L.Make_Tree_For_Pars(self.tree); _raise_if_error()
+
+    def Pars(self, b=None):
+        v = self.L.Pars(None if b is None else self.edge(b), self.tree); _raise_if_error()
+        return v
+
+    def Update_Partial_Pars(self, b, n):
+        self.L.Update_Partial_Pars(self.tree, self.edge(b), self.node(n)); _raise_if_error()
+
+    def Update_Pars_At_Given_Edge(self, b):
+        v = self.L.Update_Pars_At_Given_Edge(self.edge(b), self.tree); _raise_if_error()
+        return v
+
+    def Get_Partial_Pars(self, b, side):
+        """(ui, pars) of edge b's left (side 0) or right (1) side, or p_pars [pattern][state] in the step-matrix mode"""
+        e = self.edge(b).contents
+        d = e.left if side == 0 else e.rght
+        ip = lambda a: a.ctypes.data_as(C.c_void_p)
+        if self.tree.contents.general_pars:
+            pp = np.zeros((self.P, self.S), np.int32)
+            self.L.Get_Partial_Pars(self.tree, self.edge(b), d, None, None, ip(pp)); _raise_if_error()
+            return pp
+        ui = np.zeros(self.P, np.int32); pars = np.zeros(self.P, np.int32)
+        self.L.Get_Partial_Pars(self.tree, self.edge(b), d, ip(ui), ip(pars), None); _raise_if_error()
+        return ui, pars
+
+    @property
+    def c_pars(self):
+        return self.tree.contents.c_pars
+
+    @property
+    def site_pars(self):
+        return np.ctypeslib.as_array(self.tree.contents.site_pars, shape=(self.P,)).copy()
+
+    @property
+    def step_mat(self):
+        return np.ctypeslib.as_array(self.tree.contents.step_mat, shape=(self.S, self.S)).copy()
 
     def dLk(self, l, b):
         lv = C.c_double(l)
