@@ -2,6 +2,7 @@
 // queue and the C ABI declared in include/phyhip.h.  gfx950 only; no CPU fallback: every entry point
 // fails with PHYHIP_ERROR_NO_RESOURCE when no device is visible.
 #include "phyhip_host.hpp"
+#include "phyhip_side.hpp" // (side_release)
 
 namespace phyhip_host
 {
@@ -96,9 +97,10 @@ static void release_instance(Instance *I)
   for (hipEvent_t e : I->prof_spare) (void)hipEventDestroy(e);
   I->prof_spare.clear();
   pars_release(I);
+  side_release(I);
   void *ptrs[] = {I->d_partials, I->d_scales, I->d_tipcodes, I->d_masks, I->d_pmats, I->d_wght, I->d_invar, I->d_model,
                   I->d_site_lnl, I->d_site_lk, I->d_site_cat, I->d_fact, I->d_dot, I->d_block, I->d_result, I->d_warn, I->d_ops,
-                  I->d_pmscratch, I->d_afrag, I->d_tickets, I->d_mixexpl, I->d_dbg, I->d_tipmasks, I->d_tile_sums, I->d_big_tickets, I->d_big_stamps, I->d_big_recs, I->d_exact, I->d_anc, I->d_dist, I->d_sup_slots, I->d_sup_work};
+                  I->d_pmscratch, I->d_afrag, I->d_tickets, I->d_mixexpl, I->d_dbg, I->d_tipmasks, I->d_tile_sums, I->d_big_tickets, I->d_big_stamps, I->d_big_recs};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (I->h_result) (void)hipHostFree(I->h_result);

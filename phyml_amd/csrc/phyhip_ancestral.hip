@@ -15,7 +15,7 @@
 // tests hold it to a numpy restatement of the formula at 1e-10 relative (tests/ancestral_ref.py), the restatement to the
 // reference's printed probabilities.  log and exp are the reference's libm's (phyhip_log.hpp, phyhip_exp.hpp).
 // It writes a work space of its own: what the evaluation kernels left (site outputs, warning flag, results) stays as it was.
-#include "phyhip_host.hpp"
+#include "phyhip_side.hpp"
 #include "phyhip_layout.hpp"
 #include "phyhip_log.hpp"
 
@@ -143,34 +143,14 @@ __global__ __launch_bounds__(256) void node_posterior_kernel(const AncParams q)
     o[i] = phyhip_exp_ref((phyhip_log_ref(acc[i], phyhip_log_data) - shift) - lnl, phyhip_exp_tab);
 }
 
-// the work space of `bytes` bytes: allocated or grown on use, kept on the instance
-static int anc_reserve(Instance *I, size_t bytes)
-{
-  if (I->d_anc && I->anc_cap >= bytes) return 0;
-  if (I->d_anc) (void)hipFree(I->d_anc);
-  I->d_anc   = nullptr;
-  I->anc_cap = 0;
-  const hipError_t e = hipMalloc(&I->d_anc, bytes);
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    I->d_anc = nullptr;
-    return fail(e == hipErrorOutOfMemory ? PHYHIP_ERROR_OUT_OF_MEMORY : PHYHIP_ERROR_GENERAL,
-                "phyhip_calculate_node_state_posteriors: %zu bytes of work space: %s (ask for fewer nodes per call)", bytes, hipGetErrorString(e));
-  }
-  I->anc_cap = bytes;
-  return 0;
-}
-
 // One plain instance: its patterns of every node into out, the row of node k at out + k * out_pitch (elements)
 static int anc_run(Instance *I, int n, const int *sides, const int *mats, const double *lnl, double *out, size_t out_pitch, int *warn_out)
 {
-  if (I->class_axis || I->generic_loop)
-    return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "phyhip_calculate_node_state_posteriors: not built for %s instances",
-                I->class_axis ? "class-axis" : "generic-loop");
-  if (I->C < 1 || I->C > kMaxCategories || (I->S != 4 && I->S != 20))
-    return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "no posterior kernel for %d states x %d categories", I->S, I->C);
+  static const char *const who = "phyhip_calculate_node_state_posteriors";
   int rc;
+  if ((rc = refuse_kind(I, who, kRefuseClassAxis | kRefuseGenericLoop))) return rc;
+  if (I->C < 1 || I->C > kMaxCategories) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for %d categories", who, I->C);
+  if ((rc = refuse_kind(I, who, kRefuseStates))) return rc;
   for (int k = 0; k < 3 * n; ++k)
   {
     if ((rc = check_partial_index(I, sides[k], true))) return rc;
@@ -181,10 +161,11 @@ static int anc_run(Instance *I, int n, const int *sides, const int *mats, const 
   if ((rc = upload_masks(I))) return rc;
   // work space: the result, the caller's site log-likelihoods, the node table, the flag
   const size_t P = (size_t)I->P, S = (size_t)I->S, n_out = (size_t)n * P * S;
-  if ((rc = anc_reserve(I, (n_out + P) * sizeof(double) + ((size_t)n * 6 + 1) * sizeof(int)))) return rc;
+  auto &U = side_of(I).anc;
+  if ((rc = U.work.reserve((n_out + P) * sizeof(double) + ((size_t)n * 6 + 1) * sizeof(int), who))) return rc;
   AncParams q;
   memset(&q, 0, sizeof q);
-  q.out = (double *)I->d_anc;
+  q.out = (double *)U.work.ptr;
   double *d_lnl = q.out + n_out;
   int    *d_nodes = (int *)(d_lnl + P);
   q.warn = d_nodes + (size_t)n * 6;
@@ -203,13 +184,8 @@ static int anc_run(Instance *I, int n, const int *sides, const int *mats, const 
   q.site_lnl = lnl ? d_lnl : I->d_site_lnl; // (NULL: what the last edge evaluation left, read where it lies)
   q.P = I->P; q.Ppad = I->Ppad; q.C = I->C; q.tips = I->tips; q.layout = layout_of(I);
   q.apply_scaling = I->apply_scaling; q.invar_model = I->invar_model; q.pinvar = I->pinvar;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  if (I->prof)
-  {
-    HIPCHK(hipEventCreate(&ev[0]));
-    HIPCHK(hipEventCreate(&ev[1]));
-    HIPCHK(hipEventRecord(ev[0], I->stream));
-  }
+  SideTimer tm(I);
+  if ((rc = tm.tic())) return rc;
   const unsigned tiles = (unsigned)((I->P + 255) / 256);
   for (int first = 0; first < n; first += 65535)
   { // (a grid's second dimension holds 65535 nodes)
@@ -221,39 +197,16 @@ static int anc_run(Instance *I, int n, const int *sides, const int *mats, const 
     else hipLaunchKernelGGL(node_posterior_kernel<20>, grid, block, 0, I->stream, qc);
     HIPCHK(hipGetLastError());
   }
-  if (I->prof) HIPCHK(hipEventRecord(ev[1], I->stream));
+  if ((rc = tm.mark())) return rc;
   HIPCHK(hipStreamSynchronize(I->stream));
-  if (I->prof)
-  {
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    I->anc_prof_ms += (double)ms;
-    ++I->anc_prof_n;
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-  }
+  if ((rc = tm.toc(U.prof_ms))) return rc;
+  if (I->prof) ++U.prof_n;
   if (out_pitch == P * S) HIPCHK(hipMemcpy(out, q.out, n_out * sizeof(double), hipMemcpyDeviceToHost));
   else
     HIPCHK(hipMemcpy2D(out, out_pitch * sizeof(double), q.out, P * S * sizeof(double), P * S * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
   int w = 0;
   HIPCHK(hipMemcpy(&w, q.warn, sizeof(int), hipMemcpyDeviceToHost));
   if (w) *warn_out = 1;
-  return PHYHIP_SUCCESS;
-}
-
-static int anc_one(int instance, int n, const int *sides, const int *mats, const double *lnl, double *out, size_t out_pitch, int *warn_out)
-{
-  GET_INST(I, instance);
-  return anc_run(I, n, sides, mats, lnl, out, out_pitch, warn_out);
-}
-
-static int anc_read_profile(int instance, double *ms, int *launches)
-{
-  GET_INST(I, instance);
-  *ms += I->anc_prof_ms;
-  *launches += I->anc_prof_n;
-  I->anc_prof_ms = 0.0;
-  I->anc_prof_n  = 0;
   return PHYHIP_SUCCESS;
 }
 
@@ -270,25 +223,26 @@ int phyhip_calculate_node_state_posteriors(int instance, int nodeCount, const in
   if (nodeCount > 0 && (!sideBufferIndices || !probabilityIndices || !outPosteriors))
     return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_calculate_node_state_posteriors: a NULL array for %d nodes", nodeCount);
   int warn = 0;
-  if (Group *G = get_group(instance))
-  {
-    // (a replay of recorded queue-only calls that failed while get_group drained them is reported before any shard is touched)
-    if (const int rc = group_take_drain_error(G)) return rc;
-    const size_t pitch = (size_t)G->P * (size_t)G->S;
-    const int rc = nodeCount == 0 ? PHYHIP_SUCCESS : group_each(G, [&](int id, long long lo, long long) {
-      return anc_one(id, nodeCount, sideBufferIndices, probabilityIndices, inSiteLogLikelihoods ? inSiteLogLikelihoods + lo : nullptr,
-                     outPosteriors + (size_t)lo * G->S, pitch, &warn);
-    });
-    if (rc < 0) return rc;
+  if (nodeCount == 0)
+  { // nothing runs: a plain instance is entered all the same, a group only reports a replay that failed while it drained
+    if (Group *G = get_group(instance))
+    {
+      if (const int rc = group_take_drain_error(G)) return rc;
+    }
+    else
+    {
+      GET_INST(I, instance);
+      (void)I;
+    }
   }
   else
   {
-    GET_INST(I, instance);
-    if (nodeCount > 0)
-    {
-      const int rc = anc_run(I, nodeCount, sideBufferIndices, probabilityIndices, inSiteLogLikelihoods, outPosteriors, (size_t)I->P * I->S, &warn);
-      if (rc < 0) return rc;
-    }
+    const Group *const G = get_group_nodrain(instance); // (for the pitch of the whole only)
+    const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long lo, long long) {
+      return anc_run(I, nodeCount, sideBufferIndices, probabilityIndices, inSiteLogLikelihoods ? inSiteLogLikelihoods + lo : nullptr,
+                     outPosteriors + (size_t)lo * I->S, (size_t)(G ? G->P : I->P) * (size_t)I->S, &warn);
+    });
+    if (rc < 0) return rc;
   }
   if (outNumericalWarning) *outNumericalWarning = warn;
   return PHYHIP_SUCCESS;
@@ -298,16 +252,15 @@ int phyhip_profile_read_node_posteriors(int instance, double *outKernelMs, int *
 {
   double ms = 0.0;
   int    n = 0;
-  if (Group *G = get_group(instance))
-  {
-    const int rc = group_each(G, [&](int id, long long, long long) { return anc_read_profile(id, &ms, &n); });
-    if (rc < 0) return rc;
-  }
-  else
-  {
-    const int rc = anc_read_profile(instance, &ms, &n);
-    if (rc < 0) return rc;
-  }
+  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    auto &U = side_of(I).anc;
+    ms += U.prof_ms;
+    n += U.prof_n;
+    U.prof_ms = 0.0;
+    U.prof_n = 0;
+    return 0;
+  });
+  if (rc < 0) return rc;
   if (outKernelMs) *outKernelMs = ms;
   if (outCalls) *outCalls = n;
   return PHYHIP_SUCCESS;

@@ -23,7 +23,7 @@
 //     Dist_F_Brent line by line.  Every lane of the wave holds the same scalars; the matrix work is spread over the lanes in LDS.
 // The call writes a work space of its own: partials, scale vectors, matrices, the last evaluation's outputs and the numerical
 // warning stay what they were, and nothing queued is flushed (tips and weights are set synchronously, the model in stream order).
-#include "phyhip_host.hpp"
+#include "phyhip_side.hpp"
 #include "phyhip_layout.hpp"
 #include "phyhip_log.hpp"
 
@@ -32,7 +32,7 @@ namespace phyhip_host
 
 constexpr double kDistMax = 2.0;           // DIST_MAX, src/utilities.h:351
 constexpr int    kDistColTiles = 4;        // 16-column blocks per wave of dist_count_kernel
-// (the raw counts of one band of taxa stay below Instance::dist_band_bytes: phyhip_set_pairwise_work_space)
+// (the raw counts of one band of taxa stay below SideUnits::dist.band_bytes: phyhip_set_pairwise_work_space)
 
 typedef double dist_f64x4 __attribute__((ext_vector_type(4)));
 
@@ -348,25 +348,6 @@ template <int S> __global__ __launch_bounds__(64) void dist_opt_kernel(const Dis
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 
-// the work space of `bytes` bytes: allocated or grown on use, kept on the instance
-static int dist_reserve(Instance *I, size_t bytes)
-{
-  if (I->d_dist && I->dist_cap >= bytes) return 0;
-  if (I->d_dist) (void)hipFree(I->d_dist);
-  I->d_dist   = nullptr;
-  I->dist_cap = 0;
-  const hipError_t e = hipMalloc(&I->d_dist, bytes);
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    I->d_dist = nullptr;
-    return fail(e == hipErrorOutOfMemory ? PHYHIP_ERROR_OUT_OF_MEMORY : PHYHIP_ERROR_GENERAL,
-                "phyhip_calculate_pairwise_ml_distances: %zu bytes of work space: %s", bytes, hipGetErrorString(e));
-  }
-  I->dist_cap = bytes;
-  return 0;
-}
-
 // K80_dist(data, 1e6) / JC69_Dist of one pair from its sums (src/utilities.c:2470-2503, 2558-2581), with the host's libm
 static double dist_start_value(int S, const double *s)
 {
@@ -405,7 +386,9 @@ struct DistOut
 // sh: the plain instance, or the shards of a one-process sharded instance in pattern order
 static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, const DistOut &o)
 {
+  static const char *const who = "phyhip_calculate_pairwise_ml_distances";
   Instance *const I = sh[0];
+  auto           &U = side_of(I).dist;
   const int       n = I->tips, S = I->S;
   const size_t nn = (size_t)n * n, np = (size_t)n * (n - 1) / 2, SS = (size_t)S * S;
   for (size_t i = 0; i < nn; ++i) o.dist[i] = 0.0;
@@ -416,7 +399,7 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
   // bands of taxa
   const int    ldg = (n * S + 63) / 64 * 64;
   const size_t per_taxon = (size_t)S * ldg * sizeof(double);
-  int          band = I->dist_band_bytes / per_taxon > (size_t)n ? n : (int)(I->dist_band_bytes / per_taxon);
+  int          band = U.band_bytes / per_taxon > (size_t)n ? n : (int)(U.band_bytes / per_taxon);
   if (band < 1) band = 1;
   if (band > n - 1) band = n - 1;
   const int    nbands = (n - 1 + band - 1) / band;
@@ -429,39 +412,21 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
                off_lnl = off_dist + np, off_it = off_lnl + np, off_cnt = off_it + (np + 1) / 2, total = off_cnt + (o.counts ? band_pairs * SS : 0);
   int rc;
   if ((rc = make_current(I->dev))) return rc;
-  if ((rc = dist_reserve(I, total * sizeof(double)))) return rc;
+  if ((rc = U.work.reserve(total * sizeof(double), who))) return rc;
   if ((rc = upload_masks(I))) return rc;
   for (size_t g = 1; g < sh.size(); ++g)
   {
     if ((rc = make_current(sh[g]->dev))) return rc;
-    if ((rc = dist_reserve(sh[g], g_elems * sizeof(double)))) return rc;
+    if ((rc = side_of(sh[g]).dist.work.reserve(g_elems * sizeof(double), who))) return rc;
     if ((rc = upload_masks(sh[g]))) return rc;
   }
   if ((rc = make_current(I->dev))) return rc;
-  double *const W = (double *)I->d_dist;
+  double *const W = (double *)U.work.ptr;
   double *const d_G = W, *const d_tmp = W + off_tmp, *const d_sums = W + off_sums, *const d_init = W + off_init, *const d_dist = W + off_dist,
                *const d_lnl = W + off_lnl, *const d_cnt = o.counts ? W + off_cnt : nullptr;
   int *const    d_it = (int *)(W + off_it);
 
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  if (I->prof)
-  {
-    HIPCHK(hipEventCreate(&ev[0]));
-    HIPCHK(hipEventCreate(&ev[1]));
-  }
-  auto tic = [&]() -> int {
-    if (I->prof) HIPCHK(hipEventRecord(ev[0], I->stream));
-    return 0;
-  };
-  auto toc = [&](double &ms_sum) -> int {
-    if (!I->prof) return 0;
-    float ms = 0.0f;
-    HIPCHK(hipEventRecord(ev[1], I->stream));
-    HIPCHK(hipEventSynchronize(ev[1]));
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    ms_sum += (double)ms;
-    return 0;
-  };
+  SideTimer tm(I);
 
   DistPairParams q;
   memset(&q, 0, sizeof q);
@@ -474,13 +439,13 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
     const int  rows = (j1 - j0) * S, row_blocks = (rows + 15) / 16;
     const dim3 grid((unsigned)(ldg / 64), (unsigned)row_blocks), block(64);
     int        r2;
-    if ((r2 = tic())) return r2;
+    if ((r2 = tm.tic())) return r2;
     for (size_t g = 0; g < sh.size(); ++g)
     {
       Instance *X = sh[g];
       if ((r2 = make_current(X->dev))) return r2;
       DistCountParams c;
-      c.tip_codes = X->d_tipcodes; c.code_masks = X->d_masks; c.wght = X->d_wght; c.G = (double *)X->d_dist;
+      c.tip_codes = X->d_tipcodes; c.code_masks = X->d_masks; c.wght = X->d_wght; c.G = (double *)side_of(X).dist.work.ptr;
       c.P = X->P; c.Ppad = X->Ppad; c.n = n; c.row0 = j0 * S; c.ldg = ldg;
       HIPCHK(hipMemsetAsync(c.G, 0, (size_t)row_blocks * 16 * ldg * sizeof(double), X->stream));
       if (S == 4) hipLaunchKernelGGL(dist_count_kernel<4>, grid, block, 0, X->stream, c);
@@ -493,7 +458,7 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
     { // in shard order, on the first shard's device
       Instance *X = sh[g];
       if (X->stream != I->stream) HIPCHK(hipStreamSynchronize(X->stream));
-      const double *src = (const double *)X->d_dist;
+      const double *src = (const double *)side_of(X).dist.work.ptr;
       if (X->dev != I->dev)
       {
         HIPCHK(hipStreamSynchronize(I->stream));
@@ -511,7 +476,7 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
     if (S == 4) hipLaunchKernelGGL(dist_sums_kernel<4>, sgrid, dim3(256), 0, I->stream, s);
     else hipLaunchKernelGGL(dist_sums_kernel<20>, sgrid, dim3(256), 0, I->stream, s);
     HIPCHK(hipGetLastError());
-    return toc(I->dist_prof_count_ms);
+    return tm.toc(U.prof_count_ms);
   };
 
   std::vector<double> h_init(np), h_sums;
@@ -549,12 +514,12 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
       if ((rc = start_values())) return rc;
     DistPairParams s = q;
     s.j0 = j0; s.j1 = j1; s.pair0 = (long long)j0 * n - (long long)j0 * (j0 + 1) / 2;
-    if ((rc = tic())) return rc;
+    if ((rc = tm.tic())) return rc;
     const dim3 ogrid((unsigned)n, (unsigned)(j1 - j0));
     if (S == 4) hipLaunchKernelGGL(dist_opt_kernel<4>, ogrid, dim3(64), 0, I->stream, s);
     else hipLaunchKernelGGL(dist_opt_kernel<20>, ogrid, dim3(64), 0, I->stream, s);
     HIPCHK(hipGetLastError());
-    if ((rc = toc(I->dist_prof_opt_ms))) return rc;
+    if ((rc = tm.toc(U.prof_opt_ms))) return rc;
     if (o.counts)
     {
       const long long p1 = (long long)j1 * n - (long long)j1 * (j1 + 1) / 2;
@@ -567,12 +532,7 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
   if (o.lnl) HIPCHK(hipMemcpyAsync(o.lnl, d_lnl, np * sizeof(double), hipMemcpyDeviceToHost, I->stream));
   if (o.iters) HIPCHK(hipMemcpyAsync(o.iters, d_it, np * sizeof(int), hipMemcpyDeviceToHost, I->stream));
   HIPCHK(hipStreamSynchronize(I->stream));
-  if (I->prof)
-  {
-    ++I->dist_prof_n;
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-  }
+  if (I->prof) ++U.prof_n;
   size_t x = 0;
   for (int j = 0; j < n - 1; ++j)
     for (int k = j + 1; k < n; ++k, ++x)
@@ -580,31 +540,6 @@ static int dist_calc(const std::vector<Instance *> &sh, double min_diff_lk, cons
       o.dist[(size_t)j * n + k] = o.dist[(size_t)k * n + j] = h_dist[x];
       if (o.init) o.init[(size_t)j * n + k] = o.init[(size_t)k * n + j] = h_init[x];
     }
-  return PHYHIP_SUCCESS;
-}
-
-static int dist_enter(int instance, std::vector<Instance *> &sh)
-{
-  GET_INST(I, instance);
-  sh.push_back(I);
-  return PHYHIP_SUCCESS;
-}
-
-static int dist_set_work_space(int instance, long long max_bytes)
-{
-  GET_INST(I, instance);
-  I->dist_band_bytes = max_bytes > 0 ? (size_t)max_bytes : kDistBandBytes;
-  return PHYHIP_SUCCESS;
-}
-
-static int dist_read_profile(int instance, double *count_ms, double *opt_ms, int *calls)
-{
-  GET_INST(I, instance);
-  *count_ms += I->dist_prof_count_ms;
-  *opt_ms += I->dist_prof_opt_ms;
-  *calls += I->dist_prof_n;
-  I->dist_prof_count_ms = I->dist_prof_opt_ms = 0.0;
-  I->dist_prof_n = 0;
   return PHYHIP_SUCCESS;
 }
 
@@ -619,28 +554,13 @@ int phyhip_calculate_pairwise_ml_distances(int instance, int eigenIndex, int sta
                                            double *outCounts, double *outLogLikelihoods, int *outIterations)
 {
   if (!outDistances) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_calculate_pairwise_ml_distances: outDistances is NULL");
-  std::vector<Instance *> sh;
-  if (Group *G = get_group(instance))
-  {
-    const int rc = group_each(G, [&](int id, long long, long long) { return dist_enter(id, sh); });
-    if (rc < 0) return rc;
-  }
-  else
-  {
-    const int rc = dist_enter(instance, sh);
-    if (rc < 0) return rc;
-  }
-  if (sh.empty()) return fail(PHYHIP_ERROR_GENERAL, "phyhip_calculate_pairwise_ml_distances: an instance without shards");
+  static const char *const who = "phyhip_calculate_pairwise_ml_distances";
+  SideShards s;
   // (the refusals that belong to the kind of instance come before the ones about this call's arguments)
-  for (Instance *X : sh)
-  {
-    if (X->co)
-      return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "phyhip_calculate_pairwise_ml_distances: a rank of phyhip_comm_init_rank holds only its own patterns");
-    if (X->class_axis || X->generic_loop)
-      return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "phyhip_calculate_pairwise_ml_distances: not built for %s instances",
-                  X->class_axis ? "class-axis" : "generic-loop");
-  }
-  if (sh[0]->S != 4 && sh[0]->S != 20) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "no pairwise distance kernel for %d states", sh[0]->S);
+  int rc = side_collect(instance, who, kRefuseRank | kRefuseClassAxis | kRefuseGenericLoop, s);
+  if (rc < 0) return rc;
+  const std::vector<Instance *> &sh = s.sh;
+  if ((rc = refuse_kind(sh[0], who, kRefuseStates))) return rc;
   if (!(minDiffLk > 0.0)) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "minDiffLk %g (must be > 0)", minDiffLk);
   if (eigenIndex < 0 || eigenIndex >= sh[0]->NE) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "eigenIndex %d (0..%d)", eigenIndex, sh[0]->NE - 1);
   if (stateFrequenciesIndex < 0 || stateFrequenciesIndex >= sh[0]->NE)
@@ -650,24 +570,26 @@ int phyhip_calculate_pairwise_ml_distances(int instance, int eigenIndex, int sta
 
 int phyhip_set_pairwise_work_space(int instance, long long maxBytes)
 {
-  if (Group *G = get_group(instance)) return group_each(G, [&](int id, long long, long long) { return dist_set_work_space(id, maxBytes); });
-  return dist_set_work_space(instance, maxBytes);
+  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    side_of(I).dist.band_bytes = maxBytes > 0 ? (size_t)maxBytes : kDistBandBytes;
+    return 0;
+  });
 }
 
 int phyhip_profile_read_pairwise(int instance, double *outCountMs, double *outOptimiseMs, int *outCalls)
 {
   double a = 0.0, b = 0.0;
   int    n = 0;
-  if (Group *G = get_group(instance))
-  {
-    const int rc = group_each(G, [&](int id, long long, long long) { return dist_read_profile(id, &a, &b, &n); });
-    if (rc < 0) return rc;
-  }
-  else
-  {
-    const int rc = dist_read_profile(instance, &a, &b, &n);
-    if (rc < 0) return rc;
-  }
+  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    auto &U = side_of(I).dist;
+    a += U.prof_count_ms;
+    b += U.prof_opt_ms;
+    n += U.prof_n;
+    U.prof_count_ms = U.prof_opt_ms = 0.0;
+    U.prof_n = 0;
+    return 0;
+  });
+  if (rc < 0) return rc;
   if (outCountMs) *outCountMs = a;
   if (outOptimiseMs) *outOptimiseMs = b;
   if (outCalls) *outCalls = n;

@@ -13,7 +13,7 @@
 //     (site * (1 - pinvar) + inv * pinvar as fma(site, 1 - pinvar, inv * pinvar); log(site) - LOG2 * fact as fma(-fact, LOG2, log)),
 //   * log and exp the reference's libm's (phyhip_log.hpp, phyhip_exp.hpp).
 // It writes buffers of its own: what the evaluation kernels left (site outputs, warning flag, results) stays as it was.
-#include "phyhip_host.hpp"
+#include "phyhip_side.hpp"
 #include "phyhip_layout.hpp"
 #include "phyhip_log.hpp"
 
@@ -159,24 +159,24 @@ __global__ __launch_bounds__(256) void exact_site_kernel(const ExactParams q, co
 static int exact_run(Instance *I, int parent, int child, int pm, double *lnl, double *lk, double *cat, int *fact, double *wght_out,
                      int *warn_out)
 {
-  if (I->class_axis || I->generic_loop)
-    return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "phyhip_calculate_edge_site_outputs_exact: not built for %s instances",
-                I->class_axis ? "class-axis" : "generic-loop");
+  static const char *const who = "phyhip_calculate_edge_site_outputs_exact";
   int rc;
+  if ((rc = refuse_kind(I, who, kRefuseClassAxis | kRefuseGenericLoop))) return rc;
   if ((rc = check_partial_index(I, parent, true))) return rc;
   if ((rc = check_partial_index(I, child, true))) return rc;
   if (pm < 0 || pm >= I->nmat) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "matrix index %d", pm);
-  if (I->C < 1 || I->C > kMaxCategories || (I->S != 4 && I->S != 20))
-    return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "no exact kernel for %d states x %d categories", I->S, I->C);
+  if (I->C < 1 || I->C > kMaxCategories) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for %d categories", who, I->C);
+  if ((rc = refuse_kind(I, who, kRefuseStates))) return rc;
   devirtualise(I, parent); devirtualise(I, child);
   if ((rc = flush_sync(I))) return rc;
   if ((rc = upload_masks(I))) return rc;
   const size_t P = (size_t)I->P, nd = P * (size_t)(2 + I->C);
-  if (!I->d_exact) HIPCHK(hipMalloc(&I->d_exact, nd * sizeof(double) + (P + 1) * sizeof(int)));
+  WorkSpace &out = side_of(I).exact.out;
+  if ((rc = out.reserve(nd * sizeof(double) + (P + 1) * sizeof(int), who))) return rc;
   ExactParams q;
   memset(&q, 0, sizeof q);
   q.tip_codes = I->d_tipcodes; q.code_masks = I->d_masks; q.wght = I->d_wght; q.pi = I->d_pi; q.cat_w = I->d_catw; q.invar = I->d_invar;
-  q.site_lnl = (double *)I->d_exact; q.site_lk = q.site_lnl + P; q.site_cat = q.site_lk + P;
+  q.site_lnl = (double *)out.ptr; q.site_lk = q.site_lnl + P; q.site_cat = q.site_lk + P;
   q.fact = (int *)(q.site_cat + P * (size_t)I->C); q.warn = q.fact + P;
   q.P = I->P; q.Ppad = I->Ppad; q.C = I->C; q.tips = I->tips; q.layout = layout_of(I);
   q.parent = parent; q.child = child; q.apply_scaling = I->apply_scaling; q.invar_model = I->invar_model; q.pinvar = I->pinvar;
@@ -198,13 +198,6 @@ static int exact_run(Instance *I, int parent, int child, int pm, double *lnl, do
   HIPCHK(hipMemcpy(&w, q.warn, sizeof(int), hipMemcpyDeviceToHost));
   if (w) *warn_out = 1;
   return PHYHIP_SUCCESS;
-}
-
-static int exact_one(int instance, int parent, int child, int pm, double *lnl, double *lk, double *cat, int *fact, double *wght_out,
-                     int *warn_out)
-{
-  GET_INST(I, instance);
-  return exact_run(I, parent, child, pm, lnl, lk, cat, fact, wght_out, warn_out);
 }
 
 // the ordered sum of Lk_Core over the downloaded arrays: src/lk.c:856, patterns in ascending order, products rounded
@@ -242,23 +235,14 @@ int phyhip_calculate_edge_site_outputs_exact(int instance, int parentBufferIndex
     if (!lnl) { own_lnl.resize((size_t)P); lnl = own_lnl.data(); }
   };
   long long P = 0;
-  if (Group *G = get_group(instance))
-  {
-    host_arrays(P = G->P);
-    const int rc = group_each(G, [&](int id, long long lo, long long) {
-      return exact_one(id, parentBufferIndex, childBufferIndex, probabilityIndex, lnl ? lnl + lo : nullptr, cur_site_lk ? cur_site_lk + lo : nullptr,
-                       unscaled_site_lk_cat ? unscaled_site_lk_cat + lo * G->C : nullptr, fact_sum_scale ? fact_sum_scale + lo : nullptr,
-                       w ? w + lo : nullptr, &warn);
-    });
-    if (rc < 0) return rc;
-  }
-  else
-  {
-    GET_INST(I, instance);
-    host_arrays(P = I->P);
-    const int rc = exact_run(I, parentBufferIndex, childBufferIndex, probabilityIndex, lnl, cur_site_lk, unscaled_site_lk_cat, fact_sum_scale, w, &warn);
-    if (rc < 0) return rc;
-  }
+  const Group *const G = get_group_nodrain(instance); // (for the size of the whole only, taken when the first shard is entered)
+  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long lo, long long) {
+    if (lo == 0) host_arrays(P = G ? G->P : I->P);
+    return exact_run(I, parentBufferIndex, childBufferIndex, probabilityIndex, lnl ? lnl + lo : nullptr, cur_site_lk ? cur_site_lk + lo : nullptr,
+                     unscaled_site_lk_cat ? unscaled_site_lk_cat + lo * I->C : nullptr, fact_sum_scale ? fact_sum_scale + lo : nullptr,
+                     w ? w + lo : nullptr, &warn);
+  });
+  if (rc < 0) return rc;
   if (outSumLogLikelihood) *outSumLogLikelihood = exact_sum(w, lnl, P);
   if (outNumericalWarning) *outNumericalWarning = warn;
   return PHYHIP_SUCCESS;

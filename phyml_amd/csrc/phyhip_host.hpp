@@ -14,6 +14,8 @@
 //   phyhip_support.hip   the resampling behind SH-like branch supports, Statistics_To_SH (table, totals, draw and count kernels,
 //                        entry points of its own)
 //   phyhip_pars.hip      parsimony scores, Update_Partial_Pars / Pars (Fitch and step-matrix kernels, a queue and entry points of its own)
+//   phyhip_side.hpp      the host layer those last five share (host code only): the work space grown on use, the walk over the plain
+//                        instance or every shard, the refusals by kind of instance, the kernel timer, Instance::side
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
@@ -145,6 +147,7 @@ struct StagingRing
 
 struct Collective;
 struct ParsState;
+struct SideUnits;
 
 constexpr int kPushCmdsDefault = 3;    // uncached device memory (see Instance::push_cmds; measured against 1 / 2 / host memory, profiles/r04_latency.md)
 constexpr int kResidentDirect = 16;    // up to this many resident workgroups poll the host themselves, above that workgroup 0 relays (measured: 8 / 16 / 32, docs/history/tools/gpu_direct_ab.sh)
@@ -178,8 +181,6 @@ struct InlineDef
   int a, b, pmA, pmB;
   bool operator==(const InlineDef &o) const { return a == o.a && b == o.b && pmA == o.pmA && pmB == o.pmB; }
 };
-
-constexpr size_t kDistBandBytes = 128u << 20; // pairwise distances: the raw counts of one band of taxa stay below this by default
 
 struct Instance
 {
@@ -219,29 +220,8 @@ struct Instance
   double   *d_pi, *d_catw, *d_catr, *d_eval, *d_evec, *d_ivec;
   double   *d_site_lnl = nullptr, *d_site_lk = nullptr, *d_site_cat = nullptr, *d_dot = nullptr;
   int      *d_fact     = nullptr;
-  void     *d_exact    = nullptr; // outputs of phyhip_calculate_edge_site_outputs_exact (phyhip_exact.hip), allocated on first use
-  void     *d_anc      = nullptr; // work space of phyhip_calculate_node_state_posteriors (phyhip_ancestral.hip): grown on use, kept
-  size_t    anc_cap    = 0;       // ... its size in bytes
-  double    anc_prof_ms = 0.0;    // while profiling: time of its kernel launches (phyhip_profile_read_node_posteriors)
-  int       anc_prof_n = 0;
-  void     *d_dist     = nullptr; // work space of phyhip_calculate_pairwise_ml_distances (phyhip_dist.hip): grown on use, kept
-  size_t    dist_cap   = 0;       // ... its size in bytes
-  size_t    dist_band_bytes = kDistBandBytes; // ... and the bound on the raw counts held at a time (phyhip_set_pairwise_work_space)
-  double    dist_prof_count_ms = 0.0, dist_prof_opt_ms = 0.0; // while profiling: its count / optimise kernels (phyhip_profile_read_pairwise)
-  int       dist_prof_n = 0;
-  // phyhip_calculate_sh_support (phyhip_support.hip); all of it lives on the first shard of a sharded instance
-  void     *d_sup_slots = nullptr; // the three per-pattern vectors log_lks_aLRT[0..2], [3][P of the whole instance]: allocated on first use, kept
-  bool      sup_slot_set[3] = {false, false, false};
-  void     *d_sup_work = nullptr;  // weights, alias table, gather table, sums and flags: grown on use, kept
-  size_t    sup_work_cap = 0;
-  unsigned long long wght_epoch = 0, sup_epoch = 0; // phyhip_set_pattern_weights calls so far; their sum over the shards when the alias table was built
-  int       sup_sites = 0;         // ... and the site count it was built for
-  bool      sup_alias_valid = false, sup_table_on_device = false; // the host's table is current; d_sup_work holds it
-  long long sup_dev_P = 0;
-  std::vector<double> sup_w, sup_prob; // the weights the table was built from (all shards) and Sample_n_i_With_Proba_pi's prob
-  std::vector<int>    sup_alias;       // ... and alias
-  double    sup_prof_ms = 0.0;     // while profiling: its kernels (phyhip_profile_read_support)
-  int       sup_prof_n = 0;
+  struct SideUnits *side = nullptr; // (phyhip_side.hpp) work space and profile sums of the units beside the hot path, made on first use
+  unsigned long long wght_epoch = 0; // phyhip_set_pattern_weights calls so far (the alias table of the SH-like supports and parsimony's integer weights are made per weight vector)
   struct ParsState *pars = nullptr; // phyhip_set_parsimony (phyhip_pars.hip): planes, queue and work space of the parsimony calls
   double   *d_block    = nullptr; // [2][grid]
   double   *d_result   = nullptr; // [2]

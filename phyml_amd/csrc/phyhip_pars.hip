@@ -25,7 +25,7 @@
 // every pattern, which is order-dependent: the host layer runs that loop over the downloaded site_pars).
 // The queue of this unit is its own: no call here flushes a queued likelihood operation or writes partials, scale vectors,
 // matrices, site outputs or the warning flag, and none is a step of the call sequence the resident evaluators watch.
-#include "phyhip_host.hpp"
+#include "phyhip_side.hpp"
 #include "phyhip_layout.hpp"
 
 namespace phyhip_host
@@ -255,9 +255,7 @@ void pars_release(Instance *I)
 // the refusals that belong to the kind of instance, then "not enabled"
 static int pars_gate(const Instance *I, const char *who, bool need_state)
 {
-  if (I->co) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for a rank of phyhip_comm_init_rank", who);
-  if (I->class_axis) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for class-axis instances", who);
-  if (I->S != 4 && I->S != 20) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: no parsimony kernel for %d states", who, I->S);
+  if (const int rc = refuse_kind(I, who, kRefuseRank | kRefuseClassAxis | kRefuseStates)) return rc;
   if (need_state && !I->pars) return fail(PHYHIP_ERROR_UNINITIALIZED_INSTANCE, "%s before phyhip_set_parsimony", who);
   return 0;
 }
@@ -304,13 +302,8 @@ static int pars_launch(Instance *I, bool score, int b1, int b2, bool with_sum)
   q.tip_codes = I->d_tipcodes; q.code_masks = I->d_masks; q.fitch = T->d_fitch; q.gen = T->d_gen; q.step = T->d_step;
   q.ops = T->d_ops[s]; q.site = T->d_site; q.w = (score && with_sum) ? T->d_w : nullptr; q.sum = T->d_sum;
   q.P = I->P; q.Pp = T->Pp; q.Ppad = I->Ppad; q.n_ops = n; q.tips = I->tips; q.score = score ? 1 : 0; q.b1 = b1; q.b2 = b2;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (I->prof)
-  {
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, I->stream));
-  }
+  SideTimer tm(I); // (its pair goes to prof_pairs: collected when the profile is read)
+  if ((rc = tm.tic())) return rc;
   const dim3 grid((unsigned)((I->P + kParsTile - 1) / kParsTile));
   if (!T->general)
   {
@@ -325,8 +318,8 @@ static int pars_launch(Instance *I, bool score, int b1, int b2, bool with_sum)
   HIPCHK(hipGetLastError());
   if (I->prof)
   {
-    HIPCHK(hipEventRecord(e1, I->stream));
-    T->prof_pairs.push_back({e0, e1});
+    if ((rc = tm.mark())) return rc;
+    T->prof_pairs.push_back(tm.detach());
     ++T->prof_n;
     T->prof_updates += (double)I->P * (double)(n + (score ? 1 : 0));
   }
@@ -342,24 +335,12 @@ static int pars_launch(Instance *I, bool score, int b1, int b2, bool with_sum)
 // (phyhip_synchronize: what is queued here runs too)
 int pars_flush_queue(Instance *I) { return I->pars ? pars_launch(I, false, 0, 0, false) : 0; }
 
-static int pars_alloc(void **ptr, size_t bytes)
-{
-  const hipError_t e = hipMalloc(ptr, bytes);
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    *ptr = nullptr;
-    return fail(e == hipErrorOutOfMemory ? PHYHIP_ERROR_OUT_OF_MEMORY : PHYHIP_ERROR_GENERAL, "phyhip_set_parsimony: %zu bytes: %s", bytes,
-                hipGetErrorString(e));
-  }
-  return 0;
-}
-
 static int pars_set(Instance *I, int general, const int *step)
 {
+  static const char *const who = "phyhip_set_parsimony";
   int rc;
-  if ((rc = pars_gate(I, "phyhip_set_parsimony", false))) return rc;
-  if (general && !step) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_set_parsimony: the step-matrix mode needs a step matrix");
+  if ((rc = pars_gate(I, who, false))) return rc;
+  if (general && !step) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: the step-matrix mode needs a step matrix", who);
   ParsState *T = I->pars;
   if (!T)
   {
@@ -367,15 +348,15 @@ static int pars_set(Instance *I, int general, const int *step)
     T->Pp = (I->P + 1) & ~1ll;
     T->ninner = I->nbuf - I->tips;
     const size_t Pp = (size_t)T->Pp;
-    if ((rc = pars_alloc((void **)&T->d_site, Pp * sizeof(int)))) return rc;
-    if ((rc = pars_alloc((void **)&T->d_w, Pp * sizeof(long long)))) return rc;
-    if ((rc = pars_alloc((void **)&T->d_sum, sizeof(unsigned long long)))) return rc;
+    if ((rc = side_alloc((void **)&T->d_site, Pp * sizeof(int), who))) return rc;
+    if ((rc = side_alloc((void **)&T->d_w, Pp * sizeof(long long), who))) return rc;
+    if ((rc = side_alloc((void **)&T->d_sum, sizeof(unsigned long long), who))) return rc;
     HIPCHK(hipMemset(T->d_site, 0, Pp * sizeof(int)));
     HIPCHK(hipMemset(T->d_w, 0, Pp * sizeof(long long)));
     HIPCHK(hipHostMalloc((void **)&T->h_sum, sizeof(unsigned long long), hipHostMallocDefault));
     for (int s = 0; s < 2; ++s)
     {
-      if ((rc = pars_alloc((void **)&T->d_ops[s], (size_t)kParsStaging * sizeof(int4)))) return rc;
+      if ((rc = side_alloc((void **)&T->d_ops[s], (size_t)kParsStaging * sizeof(int4), who))) return rc;
       HIPCHK(hipHostMalloc((void **)&T->h_ops[s], (size_t)kParsStaging * sizeof(int4), hipHostMallocDefault));
       HIPCHK(hipEventCreateWithFlags(&T->ev[s], hipEventDisableTiming));
     }
@@ -395,13 +376,13 @@ static int pars_set(Instance *I, int general, const int *step)
     T->scored = false;
     if (mode == 0)
     {
-      if ((rc = pars_alloc((void **)&T->d_fitch, nin * Pp * sizeof(int2)))) return rc;
+      if ((rc = side_alloc((void **)&T->d_fitch, nin * Pp * sizeof(int2), who))) return rc;
       HIPCHK(hipMemset(T->d_fitch, 0, nin * Pp * sizeof(int2)));
     }
     else
     {
-      if ((rc = pars_alloc((void **)&T->d_gen, nin * S * Pp * sizeof(int)))) return rc;
-      if ((rc = pars_alloc((void **)&T->d_step, S * S * sizeof(int)))) return rc;
+      if ((rc = side_alloc((void **)&T->d_gen, nin * S * Pp * sizeof(int), who))) return rc;
+      if ((rc = side_alloc((void **)&T->d_step, S * S * sizeof(int), who))) return rc;
       HIPCHK(hipMemset(T->d_gen, 0, nin * S * Pp * sizeof(int)));
     }
     T->general = mode;
@@ -524,22 +505,6 @@ static int pars_get_partial(Instance *I, int buf, int *ui, int *pars, int *ppars
   return PHYHIP_SUCCESS;
 }
 
-// ---- one plain instance per call: entered as a query (nothing here is a step of the sequence the resident evaluators watch, and
-// nothing it puts on the stream touches what they read) -------------------------------------------------------------------------
-
-#define PARS_ENTER(I, id, expr)                                                                              \
-  GET_INST_RES(I, id);                                                                                       \
-  const int rc_ = (expr);                                                                                    \
-  I##_call.leave_query();                                                                                    \
-  return rc_;
-
-static int pars_set_one(int id, int general, const int *step) { PARS_ENTER(I, id, pars_set(I, general, step)) }
-static int pars_queue_one(int id, const phyhip_parsimony_operation *ops, int n) { PARS_ENTER(I, id, pars_queue(I, ops, n)) }
-static int pars_check_one(int id, int b1, int b2, bool with_sum) { PARS_ENTER(I, id, pars_score_check(I, b1, b2, with_sum)) }
-static int pars_launch_one(int id, int b1, int b2, bool with_sum) { PARS_ENTER(I, id, pars_launch(I, true, b1, b2, with_sum)) }
-static int pars_wait_one(int id, long long *sum) { PARS_ENTER(I, id, pars_wait_sum(I, sum)) }
-static int pars_site_one(int id, int *out) { PARS_ENTER(I, id, pars_get_site(I, out)) }
-static int pars_partial_one(int id, int buf, int *ui, int *pars, int *ppars) { PARS_ENTER(I, id, pars_get_partial(I, buf, ui, pars, ppars)) }
 static int pars_profile_gate(Instance *I, double *ms, int *n, double *up)
 {
   int rc;
@@ -552,23 +517,6 @@ static int pars_profile_gate(Instance *I, double *ms, int *n, double *up)
   T->prof_n = 0;
   return PHYHIP_SUCCESS;
 }
-static int pars_profile_one(int id, double *ms, int *n, double *up) { PARS_ENTER(I, id, pars_profile_gate(I, ms, n, up)) }
-
-// f(instance id, first pattern) for the plain instance or every shard of a one-process sharded one.  The group is looked up without
-// draining the queue-only likelihood calls it has recorded: they stay recorded.
-template <typename F> static int pars_each(int instance, F &&f)
-{
-  if (Group *G = get_group_nodrain(instance))
-  {
-    for (size_t g = 0; g < G->sub_id.size(); ++g)
-    {
-      const int rc = f(G->sub_id[g], G->lo[g]);
-      if (rc < 0) return rc;
-    }
-    return PHYHIP_SUCCESS;
-  }
-  return f(instance, 0ll);
-}
 
 } // namespace phyhip_host
 
@@ -576,24 +524,31 @@ using namespace phyhip_host;
 
 extern "C" {
 
+// Every entry point here walks the plain instance or every shard as a QUERY (nothing here is a step of the sequence the resident
+// evaluators watch, and nothing it puts on the stream touches what they read), and looks a group up without draining the queue-only
+// likelihood calls it has recorded: they stay recorded.
+
 int phyhip_set_parsimony(int instance, int general, const int *stepMatrix)
 {
-  return pars_each(instance, [&](int id, long long) { return pars_set_one(id, general, stepMatrix); });
+  return side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long, long long) { return pars_set(I, general, stepMatrix); });
 }
 
 int phyhip_update_partial_parsimony(int instance, const phyhip_parsimony_operation *ops, int count)
 {
-  return pars_each(instance, [&](int id, long long) { return pars_queue_one(id, ops, count); });
+  return side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long, long long) { return pars_queue(I, ops, count); });
 }
 
 int phyhip_calculate_edge_parsimony(int instance, int buffer1, int buffer2, long long *outParsimony)
 {
   const bool with_sum = outParsimony != nullptr;
-  int rc = pars_each(instance, [&](int id, long long) { return pars_check_one(id, buffer1, buffer2, with_sum); });
+  long long  sum = 0;
+  // three passes: every check of every shard, then every launch, then every wait
+  int rc = side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long, long long) { return pars_score_check(I, buffer1, buffer2, with_sum); });
   if (rc < 0) return rc;
-  if ((rc = pars_each(instance, [&](int id, long long) { return pars_launch_one(id, buffer1, buffer2, with_sum); })) < 0) return rc;
-  long long sum = 0;
-  if ((rc = pars_each(instance, [&](int id, long long) { return pars_wait_one(id, with_sum ? &sum : nullptr); })) < 0) return rc;
+  rc = side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long, long long) { return pars_launch(I, true, buffer1, buffer2, with_sum); });
+  if (rc < 0) return rc;
+  rc = side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long, long long) { return pars_wait_sum(I, with_sum ? &sum : nullptr); });
+  if (rc < 0) return rc;
   if (outParsimony) *outParsimony = sum;
   return PHYHIP_SUCCESS;
 }
@@ -601,15 +556,13 @@ int phyhip_calculate_edge_parsimony(int instance, int buffer1, int buffer2, long
 int phyhip_get_site_parsimony(int instance, int *outSitePars)
 {
   if (!outSitePars) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_get_site_parsimony: a NULL array");
-  return pars_each(instance, [&](int id, long long lo) { return pars_site_one(id, outSitePars + lo); });
+  return side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long lo, long long) { return pars_get_site(I, outSitePars + lo); });
 }
 
 int phyhip_get_partial_parsimony(int instance, int bufferIndex, int *outUi, int *outPars, int *outPPars)
 {
-  int S = 0;
-  if (Group *G = get_group_nodrain(instance)) S = G->S;
-  return pars_each(instance, [&](int id, long long lo) {
-    return pars_partial_one(id, bufferIndex, outUi ? outUi + lo : nullptr, outPars ? outPars + lo : nullptr, outPPars ? outPPars + lo * S : nullptr);
+  return side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long lo, long long) {
+    return pars_get_partial(I, bufferIndex, outUi ? outUi + lo : nullptr, outPars ? outPars + lo : nullptr, outPPars ? outPPars + lo * I->S : nullptr);
   });
 }
 
@@ -617,7 +570,7 @@ int phyhip_profile_read_parsimony(int instance, double *outKernelMs, int *outLau
 {
   double ms = 0.0, up = 0.0;
   int    n = 0;
-  const int rc = pars_each(instance, [&](int id, long long) { return pars_profile_one(id, &ms, &n, &up); });
+  const int rc = side_each<kSideNoDrain, kSideQuery>(instance, [&](Instance *I, long long, long long) { return pars_profile_gate(I, &ms, &n, &up); });
   if (rc < 0) return rc;
   if (outKernelMs) *outKernelMs = ms;
   if (outLaunches) *outLaunches = n;

@@ -22,7 +22,7 @@
 //   * support_count_kernel adds the flags (integers).
 // The call writes a work space of its own: partials, scale vectors, matrices, the last evaluation's outputs and the numerical
 // warning stay what they were.
-#include "phyhip_host.hpp"
+#include "phyhip_side.hpp"
 
 namespace phyhip_host
 {
@@ -254,76 +254,30 @@ static int support_build_alias(const std::vector<double> &w, int init_len, std::
   return 0;
 }
 
-static int support_enter_one(int instance, std::vector<Instance *> &sh)
+// the alias table of the instance's weights and `sites`, built on the host once per weight vector and site count (SideUnits::sup)
+static int support_alias(const SideShards &s, int sites, const char *who)
 {
-  GET_INST(I, instance);
-  sh.push_back(I);
-  return PHYHIP_SUCCESS;
-}
-
-// the plain instance, or the shards of a one-process sharded instance in pattern order; the refusals that belong to the kind of instance
-static int support_enter(int instance, const char *who, std::vector<Instance *> &sh, std::vector<long long> &lo, long long &P)
-{
-  if (Group *G = get_group(instance))
-  {
-    const int rc = group_each(G, [&](int id, long long first, long long) {
-      lo.push_back(first);
-      return support_enter_one(id, sh);
-    });
-    if (rc < 0) return rc;
-    P = G->P;
-  }
-  else
-  {
-    const int rc = support_enter_one(instance, sh);
-    if (rc < 0) return rc;
-    lo.push_back(0);
-    P = sh[0]->P;
-  }
-  if (sh.empty()) return fail(PHYHIP_ERROR_GENERAL, "%s: an instance without shards", who);
-  for (Instance *X : sh)
-  {
-    if (X->co) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: a rank of phyhip_comm_init_rank holds only its own patterns", who);
-    if (X->class_axis || X->generic_loop)
-      return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for %s instances", who, X->class_axis ? "class-axis" : "generic-loop");
-  }
-  return PHYHIP_SUCCESS;
-}
-
-static int support_alloc(void **ptr, size_t bytes, const char *who)
-{
-  const hipError_t e = hipMalloc(ptr, bytes);
-  if (e != hipSuccess)
-  {
-    (void)hipGetLastError();
-    *ptr = nullptr;
-    return fail(e == hipErrorOutOfMemory ? PHYHIP_ERROR_OUT_OF_MEMORY : PHYHIP_ERROR_GENERAL, "%s: %zu bytes of work space: %s", who, bytes,
-                hipGetErrorString(e));
-  }
-  return 0;
-}
-
-// the alias table of the instance's weights and `sites`, built on the host once per weight vector and site count (Instance::sup_*)
-static int support_alias(const std::vector<Instance *> &sh, const std::vector<long long> &lo, long long P, int sites, const char *who)
-{
+  const std::vector<Instance *> &sh = s.sh;
+  const long long                P = s.P;
   Instance *const    I = sh[0];
+  auto              &U = side_of(I).sup;
   unsigned long long epoch = 0;
   for (Instance *X : sh) epoch += X->wght_epoch; // (each only ever grows)
-  if (I->sup_alias_valid && I->sup_epoch == epoch && I->sup_sites == sites && (long long)I->sup_w.size() == P) return 0;
-  I->sup_alias_valid = I->sup_table_on_device = false;
-  I->sup_w.resize((size_t)P);
+  if (U.alias_valid && U.epoch == epoch && U.sites == sites && (long long)U.w.size() == P) return 0;
+  U.alias_valid = U.table_on_device = false;
+  U.w.resize((size_t)P);
   for (size_t g = 0; g < sh.size(); ++g)
   { // (weights are set synchronously: nothing queued can change them)
     int rc;
     if ((rc = make_current(sh[g]->dev))) return rc;
-    HIPCHK(hipMemcpy(I->sup_w.data() + lo[g], sh[g]->d_wght, (size_t)sh[g]->P * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(U.w.data() + s.lo[g], sh[g]->d_wght, (size_t)sh[g]->P * sizeof(double), hipMemcpyDeviceToHost));
   }
-  const int rc = support_build_alias(I->sup_w, sites, I->sup_prob, I->sup_alias);
+  const int rc = support_build_alias(U.w, sites, U.prob, U.alias);
   if (rc == -1) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: a negative pattern weight", who);
   if (rc == -2) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: every pattern weight is zero", who);
-  I->sup_epoch = epoch;
-  I->sup_sites = sites;
-  I->sup_alias_valid = true;
+  U.epoch = epoch;
+  U.sites = sites;
+  U.alias_valid = true;
   return make_current(I->dev);
 }
 
@@ -333,13 +287,14 @@ struct SupportOut
   int    *accepted;
 };
 
-static int support_calc(const std::vector<Instance *> &sh, const std::vector<long long> &lo, long long P, int sites, int replicates,
-                        unsigned long long seed, const SupportOut &o)
+static int support_calc(const SideShards &s, int sites, int replicates, unsigned long long seed, const SupportOut &o)
 {
   static const char *const who = "phyhip_calculate_sh_support";
-  Instance *const          I = sh[0];
+  Instance *const          I = s.sh[0];
+  auto                    &U = side_of(I).sup;
+  const long long          P = s.P;
   int                      rc;
-  if ((rc = support_alias(sh, lo, P, sites, who))) return rc;
+  if ((rc = support_alias(s, sites, who))) return rc;
   if ((rc = make_current(I->dev))) return rc;
   // work space: weights | prob | table (its 64-byte rows on 64-byte boundaries) | totals (4) | alias (ints) -- what depends on the
   // patterns alone, so that it stays where it was uploaded whatever the replicate count of the next call -- then sums | flags, counts (ints)
@@ -347,49 +302,31 @@ static int support_calc(const std::vector<Instance *> &sh, const std::vector<lon
   const size_t off_prob = uP, off_table = (off_prob + uP + kSupRow - 1) / kSupRow * kSupRow, off_tot = off_table + uP * kSupRow, off_alias = off_tot + 4, off_sums = off_alias + (uP + 1) / 2,
                off_int = off_sums + 3 * R;
   const size_t n_int = 2 * R + 2, total = (off_int + (n_int + 1) / 2) * sizeof(double);
-  if (!I->d_sup_work || I->sup_work_cap < total)
-  {
+  if (!U.work.holds(total))
+  { // (what is still running reads the memory about to be freed; the uploaded table goes with it)
     HIPCHK(hipStreamSynchronize(I->stream));
-    if (I->d_sup_work) (void)hipFree(I->d_sup_work);
-    I->d_sup_work = nullptr;
-    I->sup_work_cap = 0;
-    I->sup_table_on_device = false;
-    if ((rc = support_alloc(&I->d_sup_work, total, who))) return rc;
-    I->sup_work_cap = total;
+    U.table_on_device = false;
+    if ((rc = U.work.reserve(total, who))) return rc;
   }
-  double *const W = (double *)I->d_sup_work;
+  double *const W = (double *)U.work.ptr;
   int *const    d_alias = (int *)(W + off_alias), *const Wi = (int *)(W + off_int);
   SupportParams q;
   memset(&q, 0, sizeof q);
-  q.slots = (const double *)I->d_sup_slots; q.wght = W; q.prob = W + off_prob; q.alias = d_alias; q.table = W + off_table; q.totals = W + off_tot;
+  q.slots = (const double *)U.slots.ptr; q.wght = W; q.prob = W + off_prob; q.alias = d_alias; q.table = W + off_table; q.totals = W + off_tot;
   q.sums = o.sums ? W + off_sums : nullptr; q.flags = Wi; q.counts = Wi + 2 * R;
   q.P = P; q.sites = sites; q.replicates = replicates;
   q.key0 = (uint32_t)seed; q.key1 = (uint32_t)(seed >> 32);
-  if (!I->sup_table_on_device || I->sup_dev_P != P)
+  if (!U.table_on_device || U.dev_P != P)
   { // (pageable memory: the copies have left the host vectors when the calls return)
-    HIPCHK(hipMemcpyAsync(W, I->sup_w.data(), uP * sizeof(double), hipMemcpyHostToDevice, I->stream));
-    HIPCHK(hipMemcpyAsync(W + off_prob, I->sup_prob.data(), uP * sizeof(double), hipMemcpyHostToDevice, I->stream));
-    HIPCHK(hipMemcpyAsync(d_alias, I->sup_alias.data(), uP * sizeof(int), hipMemcpyHostToDevice, I->stream));
+    HIPCHK(hipMemcpyAsync(W, U.w.data(), uP * sizeof(double), hipMemcpyHostToDevice, I->stream));
+    HIPCHK(hipMemcpyAsync(W + off_prob, U.prob.data(), uP * sizeof(double), hipMemcpyHostToDevice, I->stream));
+    HIPCHK(hipMemcpyAsync(d_alias, U.alias.data(), uP * sizeof(int), hipMemcpyHostToDevice, I->stream));
     HIPCHK(hipStreamSynchronize(I->stream));
-    I->sup_table_on_device = true;
-    I->sup_dev_P = P;
+    U.table_on_device = true;
+    U.dev_P = P;
   }
-  struct Events
-  { // (destroyed on every way out)
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~Events()
-    {
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  hipEvent_t *const ev = evs.e;
-  if (I->prof)
-  {
-    HIPCHK(hipEventCreate(&ev[0]));
-    HIPCHK(hipEventCreate(&ev[1]));
-    HIPCHK(hipEventRecord(ev[0], I->stream));
-  }
+  SideTimer tm(I);
+  if ((rc = tm.tic())) return rc;
   hipLaunchKernelGGL(support_table_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, I->stream, q);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(support_totals_kernel, dim3(1), dim3(64), 0, I->stream, q);
@@ -399,7 +336,7 @@ static int support_calc(const std::vector<Instance *> &sh, const std::vector<lon
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(support_count_kernel, dim3(1), dim3(256), 0, I->stream, q);
   HIPCHK(hipGetLastError());
-  if (I->prof) HIPCHK(hipEventRecord(ev[1], I->stream));
+  if ((rc = tm.mark())) return rc;
   int    counts[2] = {0, 0};
   double totals[3];
   HIPCHK(hipMemcpyAsync(counts, q.counts, sizeof counts, hipMemcpyDeviceToHost, I->stream));
@@ -407,13 +344,8 @@ static int support_calc(const std::vector<Instance *> &sh, const std::vector<lon
   if (o.sums) HIPCHK(hipMemcpyAsync(o.sums, q.sums, 3 * R * sizeof(double), hipMemcpyDeviceToHost, I->stream));
   if (o.accepted) HIPCHK(hipMemcpyAsync(o.accepted, q.flags, R * sizeof(int), hipMemcpyDeviceToHost, I->stream));
   HIPCHK(hipStreamSynchronize(I->stream));
-  if (I->prof)
-  {
-    float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    I->sup_prof_ms += (double)ms;
-    ++I->sup_prof_n;
-  }
+  if ((rc = tm.toc(U.prof_ms))) return rc;
+  if (I->prof) ++U.prof_n;
   if (o.sh) *o.sh = (double)counts[0] / (double)replicates;     // res = nb / occurence
   if (o.rell) *o.rell = (double)counts[1] / (double)replicates;
   if (o.totals)
@@ -421,10 +353,14 @@ static int support_calc(const std::vector<Instance *> &sh, const std::vector<lon
   return PHYHIP_SUCCESS;
 }
 
-static int support_set_slot(const std::vector<Instance *> &sh, const std::vector<long long> &lo, long long P, int slot, const double *in)
+static int support_set_slot(const SideShards &s, int slot, const double *in)
 {
   static const char *const who = "phyhip_set_support_site_log_likelihoods";
+  const std::vector<Instance *> &sh = s.sh;
+  const std::vector<long long>  &lo = s.lo;
+  const long long          P = s.P;
   Instance *const          I = sh[0];
+  auto                    &U = side_of(I).sup;
   int                      rc;
   if (in == nullptr)
     for (Instance *X : sh)
@@ -433,12 +369,12 @@ static int support_set_slot(const std::vector<Instance *> &sh, const std::vector
       if ((rc = flush_sync(X))) return rc;
     }
   if ((rc = make_current(I->dev))) return rc;
-  if (!I->d_sup_slots)
+  if (!U.slots.ptr)
   {
-    if ((rc = support_alloc(&I->d_sup_slots, 3 * (size_t)P * sizeof(double), who))) return rc;
-    I->sup_slot_set[0] = I->sup_slot_set[1] = I->sup_slot_set[2] = false;
+    if ((rc = U.slots.reserve(3 * (size_t)P * sizeof(double), who))) return rc;
+    U.slot_set[0] = U.slot_set[1] = U.slot_set[2] = false;
   }
-  double *const dst = (double *)I->d_sup_slots + (size_t)slot * (size_t)P;
+  double *const dst = (double *)U.slots.ptr + (size_t)slot * (size_t)P;
   HIPCHK(hipStreamSynchronize(I->stream)); // (a resampling still reading the slot)
   if (in)
   {
@@ -452,17 +388,7 @@ static int support_set_slot(const std::vector<Instance *> &sh, const std::vector
       if (X->dev == I->dev) HIPCHK(hipMemcpy(dst + lo[g], X->d_site_lnl, bytes, hipMemcpyDeviceToDevice));
       else HIPCHK(hipMemcpyPeer(dst + lo[g], I->dev, X->d_site_lnl, X->dev, bytes));
     }
-  I->sup_slot_set[slot] = true;
-  return PHYHIP_SUCCESS;
-}
-
-static int support_read_profile(int instance, double *ms, int *calls)
-{
-  GET_INST(I, instance);
-  *ms += I->sup_prof_ms;
-  *calls += I->sup_prof_n;
-  I->sup_prof_ms = 0.0;
-  I->sup_prof_n = 0;
+  U.slot_set[slot] = true;
   return PHYHIP_SUCCESS;
 }
 
@@ -472,44 +398,43 @@ using namespace phyhip_host;
 
 extern "C" {
 
+// (every entry point: the plain instance or the shards in pattern order, and the refusals that belong to the kind of instance)
+constexpr unsigned kSupportRefuses = kRefuseRank | kRefuseClassAxis | kRefuseGenericLoop;
+
 int phyhip_set_support_site_log_likelihoods(int instance, int slot, const double *inSiteLogLikelihoods)
 {
-  std::vector<Instance *> sh;
-  std::vector<long long>  lo;
-  long long               P = 0;
-  const int rc = support_enter(instance, "phyhip_set_support_site_log_likelihoods", sh, lo, P);
+  SideShards s;
+  const int  rc = side_collect(instance, "phyhip_set_support_site_log_likelihoods", kSupportRefuses, s);
   if (rc < 0) return rc;
   if (slot < 0 || slot > 2) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_set_support_site_log_likelihoods: slot %d (0..2)", slot);
-  return support_set_slot(sh, lo, P, slot, inSiteLogLikelihoods);
+  return support_set_slot(s, slot, inSiteLogLikelihoods);
 }
 
 int phyhip_calculate_sh_support(int instance, int siteCount, int replicateCount, unsigned long long seed, double *outSH, double *outRELL,
                                 double *outTotals, double *outReplicateSums, int *outAccepted)
 {
-  std::vector<Instance *> sh;
-  std::vector<long long>  lo;
-  long long               P = 0;
-  const int rc = support_enter(instance, "phyhip_calculate_sh_support", sh, lo, P);
+  SideShards s;
+  const int  rc = side_collect(instance, "phyhip_calculate_sh_support", kSupportRefuses, s);
   if (rc < 0) return rc;
   if (siteCount <= 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_calculate_sh_support: siteCount %d (must be > 0)", siteCount);
   if (replicateCount <= 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_calculate_sh_support: replicateCount %d (must be > 0)", replicateCount);
+  const auto &U = side_of(s.sh[0]).sup;
   for (int k = 0; k < 3; ++k)
-    if (!sh[0]->d_sup_slots || !sh[0]->sup_slot_set[k])
+    if (!U.slots.ptr || !U.slot_set[k])
       return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_calculate_sh_support: slot %d was never set (phyhip_set_support_site_log_likelihoods)", k);
-  return support_calc(sh, lo, P, siteCount, replicateCount, seed, SupportOut{outSH, outRELL, outTotals, outReplicateSums, outAccepted});
+  return support_calc(s, siteCount, replicateCount, seed, SupportOut{outSH, outRELL, outTotals, outReplicateSums, outAccepted});
 }
 
 int phyhip_get_support_alias_table(int instance, int siteCount, double *outProb, int *outAlias)
 {
-  std::vector<Instance *> sh;
-  std::vector<long long>  lo;
-  long long               P = 0;
-  int rc = support_enter(instance, "phyhip_get_support_alias_table", sh, lo, P);
+  SideShards s;
+  int        rc = side_collect(instance, "phyhip_get_support_alias_table", kSupportRefuses, s);
   if (rc < 0) return rc;
   if (siteCount <= 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_get_support_alias_table: siteCount %d (must be > 0)", siteCount);
-  if ((rc = support_alias(sh, lo, P, siteCount, "phyhip_get_support_alias_table"))) return rc;
-  if (outProb) memcpy(outProb, sh[0]->sup_prob.data(), (size_t)P * sizeof(double));
-  if (outAlias) memcpy(outAlias, sh[0]->sup_alias.data(), (size_t)P * sizeof(int));
+  if ((rc = support_alias(s, siteCount, "phyhip_get_support_alias_table"))) return rc;
+  const auto &U = side_of(s.sh[0]).sup;
+  if (outProb) memcpy(outProb, U.prob.data(), (size_t)s.P * sizeof(double));
+  if (outAlias) memcpy(outAlias, U.alias.data(), (size_t)s.P * sizeof(int));
   return PHYHIP_SUCCESS;
 }
 
@@ -517,16 +442,15 @@ int phyhip_profile_read_support(int instance, double *outKernelMs, int *outCalls
 {
   double ms = 0.0;
   int    n = 0;
-  if (Group *G = get_group(instance))
-  {
-    const int rc = group_each(G, [&](int id, long long, long long) { return support_read_profile(id, &ms, &n); });
-    if (rc < 0) return rc;
-  }
-  else
-  {
-    const int rc = support_read_profile(instance, &ms, &n);
-    if (rc < 0) return rc;
-  }
+  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    auto &U = side_of(I).sup;
+    ms += U.prof_ms;
+    n += U.prof_n;
+    U.prof_ms = 0.0;
+    U.prof_n = 0;
+    return 0;
+  });
+  if (rc < 0) return rc;
   if (outKernelMs) *outKernelMs = ms;
   if (outCalls) *outCalls = n;
   return PHYHIP_SUCCESS;

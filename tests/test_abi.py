@@ -154,13 +154,16 @@ def test_resident_choke_point():
     instance table is private, so an entry point reaches an Instance only through an `Entered<...>` object (GET_INST /
     GET_INST_RES) whose constructor is the choke point, and the three ways back to "clean" are members of `Entered<true>` only
     (a static_assert in each: test_choke_point_is_a_compile_time_property compiles the counter-example).  What is left to review
-    by list is WHICH entry points declare themselves resident-aware, and which of the three ways back each one takes."""
+    by list is WHICH entry points declare themselves resident-aware, and which of the three ways back each one takes.  An entry
+    point that walks the plain instance or every shard through the query form of phyhip_side.hpp's walker (side_each<..., kSideQuery>:
+    Entered<true>, then leave_query once the visit has returned) declares itself so in every shard and is reviewed here like the rest."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     import glob
     csrc = os.path.join(root, "phyml_amd", "csrc")
     units = sorted(glob.glob(os.path.join(csrc, "phyhip*.hip")))
-    src = "".join(open(f).read() for f in [os.path.join(csrc, "phyhip_host.hpp"), os.path.join(csrc, "phyhip_shard.hpp")] + units)
+    headers = [os.path.join(csrc, h) for h in ("phyhip_host.hpp", "phyhip_shard.hpp", "phyhip_side.hpp")]
+    src = "".join(open(f).read() for f in headers + units)
     ext = "".join(t[t.index('extern "C" {'):] for t in (open(f).read() for f in units) if 'extern "C" {' in t)
     heads = [(m.start(), m.group(1)) for m in re.finditer(r'^(?:int|const char \*)\s*(phyhip_[a-z_0-9]+)\(', ext, flags=re.M)]
     bodies = {}
@@ -168,18 +171,37 @@ def test_resident_choke_point():
         bodies[name] = ext[a:nxt[0]]
     from phyml_amd import capi
     assert set(capi.SYMBOLS) <= set(bodies), sorted(set(capi.SYMBOLS) - set(bodies))
-    keepers = {name for name, body in bodies.items() if "GET_INST_RES(" in body}
+    walks_as_query = lambda body: re.search(r"side_each<\s*\w+\s*,\s*kSideQuery\s*>\(", body) is not None
+    keepers = {name for name, body in bodies.items() if "GET_INST_RES(" in body or walks_as_query(body)}
     assert keepers == {"phyhip_update_transition_matrices", "phyhip_set_transition_matrix", "phyhip_update_partials",
                        "phyhip_update_eigen_lr", "phyhip_calculate_edge_log_likelihoods", "phyhip_calculate_eigen_lnl_dlnl",
                        "phyhip_calculate_eigen_lnl", "phyhip_get_numerical_warning", "phyhip_get_resident_stats",
-                       "phyhip_get_big_resident_stats", "phyhip_get_virtual_stats", "phyhip_profile_read_kernel"}, sorted(keepers)
+                       "phyhip_get_big_resident_stats", "phyhip_get_virtual_stats", "phyhip_profile_read_kernel",
+                       "phyhip_set_parsimony", "phyhip_update_partial_parsimony", "phyhip_calculate_edge_parsimony",
+                       "phyhip_get_site_parsimony", "phyhip_get_partial_parsimony", "phyhip_profile_read_parsimony"}, sorted(keepers)
     REVIEWED = {"leave_queued_only": {"phyhip_update_transition_matrices", "phyhip_set_transition_matrix", "phyhip_update_partials"},
                 "leave_untouched": {"phyhip_calculate_eigen_lnl_dlnl", "phyhip_calculate_eigen_lnl"},
                 "leave_query": {"phyhip_get_numerical_warning", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats",
-                                "phyhip_get_virtual_stats", "phyhip_profile_read_kernel"}}
+                                "phyhip_get_virtual_stats", "phyhip_profile_read_kernel",
+                                "phyhip_set_parsimony", "phyhip_update_partial_parsimony", "phyhip_calculate_edge_parsimony",
+                                "phyhip_get_site_parsimony", "phyhip_get_partial_parsimony", "phyhip_profile_read_parsimony"}}
     for helper, allowed in REVIEWED.items():
-        users = {name for name, body in bodies.items() if "." + helper + "(" in body}
+        users = {name for name, body in bodies.items() if "." + helper + "(" in body or (helper == "leave_query" and walks_as_query(body))}
         assert users == allowed, (helper, sorted(users ^ allowed))
+    # ... and the scan above sees every one of them: outside the extern "C" bodies nothing declares itself resident-aware or takes a
+    # way back, but the walker (its query form takes leave_query, once, after the visit) and phyhip_host.hpp's own definitions
+    ways = (".leave_query(", ".leave_untouched(", ".leave_queued_only(")
+    for f in units + headers[1:2]:
+        t = open(f).read()
+        outside = t[:t.index('extern "C" {')] if 'extern "C" {' in t else t
+        assert "GET_INST_RES(" not in outside and not any(w in outside for w in ways), f
+    host = open(headers[0]).read()
+    assert host.count("GET_INST_RES(") == 1 and "#define GET_INST_RES(I, id)" in host and not any(w in host for w in ways)
+    side = open(headers[2]).read()
+    assert "GET_INST_RES(" not in side and side.count(".leave_query(") == 1 and not any(w in side for w in ways[1:])
+    walker = side[side.index("int side_one("):side.index("int side_each(")]
+    assert "GET_INST_AS(I, id, Query);" in walker and "if constexpr (Query) I_call.leave_query();" in walker
+    assert len(re.findall(r"GET_INST_AS\(", src)) == 4  # (its definition, GET_INST, GET_INST_RES, the walker)
     # the kernels that write the matrix table outside the traversal launches run behind the large-grid resident workgroups' exit --
     # both are reachable from entry points that keep those workgroups (GET_INST_RES: the two matrix setters)
     q = open(os.path.join(csrc, "phyhip_queue.hip")).read()

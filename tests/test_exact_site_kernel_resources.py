@@ -10,13 +10,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def exact_kernels(tmp_path_factory):
-    import __graft_entry__ as g
-    g.build()
     import test_kernel_resources as kr
-    if not os.path.exists(os.path.join(kr.LLVM, "llvm-objdump")):
-        pytest.fail("the ROCm LLVM tools are needed to read the code objects")
-    k = kr.kernels_of(kr.LIB, str(tmp_path_factory.mktemp("kres_exact")))
-    return {n: v for n, v in k.items() if "exact_site" in n}
+    return kr.product_kernels(tmp_path_factory, "exact_site", build=True)
 
 
 def test_both_instantiations_are_there(exact_kernels):

@@ -38,9 +38,26 @@ def kernels_of(path, tmp):
     return out
 
 
+_PARSED = {}   # the product library's kernels, disassembled once per process
+
+
+def product_kernels(tmp_path_factory, *stems, build=False):
+    """kernels_of(LIB), cached; with `stems` only the kernels whose name holds one of them.  build: the library is built first (a
+    no-op when it is current) and missing LLVM tools are a failure, not a skip -- what the tests of the units beside the hot path
+    (tests/test_*_kernel_resources.py) ask for."""
+    if build:
+        import __graft_entry__ as g
+        g.build()
+        if not os.path.exists(os.path.join(LLVM, "llvm-objdump")):
+            pytest.fail("the ROCm LLVM tools are needed to read the code objects")
+    if LIB not in _PARSED:
+        _PARSED[LIB] = kernels_of(LIB, str(tmp_path_factory.mktemp("kres")))
+    return {n: v for n, v in _PARSED[LIB].items() if not stems or any(s in n for s in stems)}
+
+
 @pytest.fixture(scope="module")
 def product(tmp_path_factory):
-    k = kernels_of(LIB, str(tmp_path_factory.mktemp("kres")))
+    k = product_kernels(tmp_path_factory)
     assert len(k) > 80, len(k)
     return k
 

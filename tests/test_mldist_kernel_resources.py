@@ -11,13 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def dist_kernels(tmp_path_factory):
-    import __graft_entry__ as g
-    g.build()
     import test_kernel_resources as kr
-    if not os.path.exists(os.path.join(kr.LLVM, "llvm-objdump")):
-        pytest.fail("the ROCm LLVM tools are needed to read the code objects")
-    k = kr.kernels_of(kr.LIB, str(tmp_path_factory.mktemp("kres_mldist")))
-    return {n: v for n, v in k.items() if "dist_count_kernel" in n or "dist_sums_kernel" in n or "dist_opt_kernel" in n or "dist_add_kernel" in n}
+    return kr.product_kernels(tmp_path_factory, "dist_count_kernel", "dist_sums_kernel", "dist_opt_kernel", "dist_add_kernel", build=True)
 
 
 def test_every_instantiation_is_there(dist_kernels):

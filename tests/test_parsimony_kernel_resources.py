@@ -14,13 +14,8 @@ STEMS = ("pars_fitch_kernel", "pars_general_kernel")
 
 @pytest.fixture(scope="module")
 def pars_kernels(tmp_path_factory):
-    import __graft_entry__ as g
-    g.build()
     import test_kernel_resources as kr
-    if not os.path.exists(os.path.join(kr.LLVM, "llvm-objdump")):
-        pytest.fail("the ROCm LLVM tools are needed to read the code objects")
-    k = kr.kernels_of(kr.LIB, str(tmp_path_factory.mktemp("kres_pars")))
-    return {n: v for n, v in k.items() if any(s in n for s in STEMS)}
+    return kr.product_kernels(tmp_path_factory, *STEMS, build=True)
 
 
 def test_both_kernels_are_there_once_per_state_count(pars_kernels):

@@ -12,13 +12,8 @@ STEMS = ("support_table_kernel", "support_totals_kernel", "support_draw_kernel",
 
 @pytest.fixture(scope="module")
 def support_kernels(tmp_path_factory):
-    import __graft_entry__ as g
-    g.build()
     import test_kernel_resources as kr
-    if not os.path.exists(os.path.join(kr.LLVM, "llvm-objdump")):
-        pytest.fail("the ROCm LLVM tools are needed to read the code objects")
-    k = kr.kernels_of(kr.LIB, str(tmp_path_factory.mktemp("kres_support")))
-    return {n: v for n, v in k.items() if any(s in n for s in STEMS)}
+    return kr.product_kernels(tmp_path_factory, *STEMS, build=True)
 
 
 def test_every_kernel_is_there_once(support_kernels):
