@@ -471,6 +471,38 @@ int phyhip_calculate_eigen_lnl(int instance, double l, double *outLnL);
 
 int phyhip_get_dot_prod(int instance, double *outDotProd);
 
+/* Br_Len_Opt's search on one edge -- Br_Len_Spline, src/optimiz.c:2244-2470 -- in ONE device call: every probe of the branch
+   length is a dLk on the products phyhip_update_eigen_lr has left (the precondition of phyhip_calculate_eigen_lnl_dlnl), and the
+   reference's control flow runs in the kernel itself (one workgroup, one plain launch; phyml_amd/csrc/phyhip_brlen.hip).
+     *l          in: the start length, as the caller holds it (not clamped).  out: best_l, the reference's *l on return
+     initLnL     tree->c_lnL on entry: the caller's Lk(b) of the edge (what fv becomes when the first derivative is already
+                 negative, and what best_lnL starts from)
+     iterMax     mod->s_opt->brent_it_max (1 .. BRENT_IT_MAX = 1000), tol: mod->s_opt->min_diff_lk_local (> 0)
+     outLnL      best_lnL; outDLnL: tree->c_dlnL as the search leaves it (the last probe's, or the first one's where the upper
+                 walk ends before its first probe); outEvaluations: the dLk evaluations taken
+     outStatus   0 the spline step was taken; 1 / 2 returned from the lower / upper bracket walk (:2280-2285, :2308-2313); where the
+                 reference stops the program: 3 no acceptable root (:2372-2376), 4 bracket invariant broken (:2423-2425),
+                 5 iter == iterMax (:2463), 6 a NaN length (src/lk.c:671), 7 a bracket walk longer than the host-computed bound
+                 of ceil(log(l_max / l_min) / log 1.2) + 2 trips (cannot happen in exact arithmetic)
+   Flushes the queue as phyhip_calculate_eigen_lnl_dlnl does, then waits for the stream.  Reads dot_prod and the instance's
+   constants; the numerical warning becomes that of the search's last evaluation; partials, matrices, site outputs, dot_prod and
+   the queue are left alone.  A plain call: the large-grid resident workgroups leave, the next resident-served call re-validates
+   the stream.  Any out pointer may be NULL.
+     Not built (PHYHIP_ERROR_NO_IMPLEMENTATION, nothing launched; the caller drives phyhip_calculate_eigen_lnl_dlnl itself, as
+   the host layer's Br_Len_Opt does): ranks of phyhip_comm_init_rank, one-process sharded instances (each probe needs every shard's
+   sums), PHYHIP_FLAG_CLASS_AXIS instances and any instance of more than one eigen system, PHYHIP_FLAG_GENERIC_LOOP instances,
+   states other than 4 / 20, more than 8 categories (the expl table of one evaluation holds 8), more than 16 384 patterns.  That
+   last bound is what the call is built and tested for, NOT where it is faster: measured against the chain of
+   phyhip_calculate_eigen_lnl_dlnl calls it won at one of thirteen shapes (54 taxa x 382 nucleotide patterns with 22 long searches,
+   by 5 % of a pass; searches of more than 8 probes on at most 382 patterns are faster by a quarter, shorter ones slower) and lost
+   at every other (profiles/brlen_opt.md); the host layer's Br_Len_Opt takes it only where its caller asks.  NaN *l or initLnL:
+   PHYHIP_ERROR_FLOATING_POINT.  iterMax outside 1 .. 1000, tol <= 0: PHYHIP_ERROR_OUT_OF_RANGE. */
+int phyhip_optimise_edge_length(int instance, double *l, double initLnL, int iterMax, double tol,
+                                double *outLnL, double *outDLnL, int *outEvaluations, int *outStatus);
+/* while phyhip_profile(instance, 1): milliseconds of the search kernel (HIP events on the instance's stream), the calls and the
+   evaluations they took since the previous read; reading resets all three */
+int phyhip_profile_read_edge_length(int instance, double *outKernelMs, int *outCalls, long long *outEvaluations);
+
 /* ---- multi-GPU, one process per GPU (MPI-style hosts; PhyML's MPI build runs one process per rank) -------------- */
 
 /* ncclGetUniqueId: rank 0 calls it and broadcasts the PHYHIP_UNIQUE_ID_BYTES bytes by whatever means the host has (MPI_Bcast). */

@@ -15,6 +15,9 @@
  *   Update_Eigen_Lr(b,tree)         src/lk.c:1038
  *   Set_Both_Sides / Set_Use_Eigen_Lr / Set_Update_Eigen_Lr   src/utilities.c:11614-11640
  *   Make_Tree_For_Lk / Free_Tree_Lk src/make.c:17 / src/free.c:387   (device instance instead of the host slab)
+ *   Br_Len_Opt(&l,b,tree)           src/optimiz.c:607 one edge's length optimised: Lk(b) with update_eigen_lr, Br_Len_Spline
+ *                                   (src/optimiz.c:2244) driving dLk() from the host or, where the caller asks for it, in ONE
+ *                                   device call (phyhip_optimise_edge_length): the same steps; then the matrix refresh
  *   Br_Len_Newton(&l,b,tree)        NOT a reference function: a harness that drives the surface the way the caller
  *                                   Br_Len_Opt (src/optimiz.c:607-663) does -- Lk(b) with update_eigen_lr, then dLk alone,
  *                                   then the matrix refresh -- with a safeguarded Newton search on dlnL in place of the
@@ -71,6 +74,9 @@ typedef struct __Model
   int     use_m4mod;             /* mod->use_m4mod (`phyml --cov`, src/cl.c:753-757): Update_Partial_Lk sends the data through the
                                     generic loop instead of the SIMD kernels, src/lk.c:1303-1324 -- the device instance is then
                                     created with PHYHIP_FLAG_GENERIC_LOOP (that loop's arithmetic) */
+  /* Br_Len_Opt (appended, every offset above stays what it was; Make_Model_Basic sets the reference's defaults, src/init.c:760,770) */
+  phydbl  min_diff_lk_local;     /* mod->s_opt->min_diff_lk_local: 1.E-03 */
+  int     brent_it_max;          /* mod->s_opt->brent_it_max: BRENT_IT_MAX */
 } t_mod;
 
 typedef struct __Tree
@@ -112,9 +118,18 @@ typedef struct __Tree
   int     *step_mat;          /* tree->step_mat [ns][ns], row = parent state: Get_Step_Mat's for 4 states and 0/1 otherwise, or the caller's
                                  own, set before Make_Tree_For_Pars (amino acids: the reference's table is PhyML's to pass in) */
   short    own_step_mat;      /* step_mat was allocated by Get_Step_Mat (Free_Tree_Pars frees it) */
+  /* Br_Len_Opt (src/optimiz.c:607): appended, every offset above stays what it was */
+  int      n_tot_bl_opt;      /* tree->n_tot_bl_opt: grows by one per step of Br_Len_Spline, as in the reference (the evaluations after
+                                 the first, plus one where a bracket walk leaves [l_min, l_max] before its probe) */
+  int      bl_opt_evaluations, bl_opt_status; /* of the last Br_Len_Opt: dLk evaluations taken; phyhip_optimise_edge_length's status */
+  short    bl_opt_host_chain;  /* the route of Br_Len_Opt's search.  NO and YES: dLk() driven from the host, one round trip per probe -- the default,
+                                 measured the faster route on all but one shape (profiles/brlen_opt.md); 2: the device call wherever it
+                                 is built, the host-driven steps where it is not (the search is the same on both routes, probe by probe) */
+  short    bl_opt_on_device;   /* the last Br_Len_Opt's search was the device call */
 } t_tree;
 
 #define PHL_N_SPARE 4
+#define BRENT_IT_MAX 1000 /* src/utilities.h:337 */
 
 /* ---- construction ------------------------------------------------------------------------------ */
 
@@ -158,6 +173,16 @@ void   Update_Eigen_Lr(t_edge *b, t_tree *tree);
 void   Set_Both_Sides(int yesno, t_tree *tree);
 void   Set_Use_Eigen_Lr(int yesno, t_tree *tree);
 void   Set_Update_Eigen_Lr(int yesno, t_tree *tree);
+/* Br_Len_Opt, src/optimiz.c:607-663: Set_Update_Eigen_Lr(YES) / Set_Use_Eigen_Lr(NO), lk_begin = Lk(b), the flags swapped, the search,
+   Update_PMat_At_Given_Edge(b), both flags NO, then the decrease check of :656-661 through the exit handler.  The search is the
+   step function of phyml_amd/csrc/phyhip_brlen_step.h driving dLk(): every evaluation on the device, one round trip per probe.
+   With tree->bl_opt_host_chain = 2 it is phyhip_optimise_edge_length instead -- the same steps inside one kernel -- wherever that
+   call is built (not: sharded, class-axis and generic-loop instances, more patterns than it serves); measured, that route is the
+   faster one only on small nucleotide alignments with many long searches (profiles/brlen_opt.md), so it is not the default.
+   *l, b->l, tree->c_lnL, tree->c_dlnL, tree->numerical_warning and tree->n_tot_bl_opt end as the reference leaves them; where the
+   reference stops the program (statuses 3-7) the exit handler runs with its wording.  Optimize_Br_Len_Serie and MIXT_Br_Len_Opt
+   stay with the caller. */
+phydbl Br_Len_Opt(phydbl *l, t_edge *b, t_tree *tree);
 phydbl Br_Len_Newton(phydbl *l, t_edge *b, t_tree *tree);
 /* host P-matrix (src/models.c:257-326, 353-373) -- used when tree->host_pmat == YES */
 void   PMat(phydbl l, const t_mod *mod, int pos, phydbl *Pij);

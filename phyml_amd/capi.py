@@ -52,6 +52,7 @@ SYMBOLS = [
     "phyhip_set_support_site_log_likelihoods", "phyhip_calculate_sh_support", "phyhip_get_support_alias_table", "phyhip_profile_read_support",
     "phyhip_set_parsimony", "phyhip_update_partial_parsimony", "phyhip_calculate_edge_parsimony", "phyhip_get_site_parsimony",
     "phyhip_get_partial_parsimony", "phyhip_profile_read_parsimony",
+    "phyhip_optimise_edge_length", "phyhip_profile_read_edge_length",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -61,6 +62,11 @@ PARS_TILE = 256  # kParsTile of phyml_amd/csrc/phyhip_pars.hip: patterns per wor
 PARS_STAGING = 4096  # kParsStaging: operations one parsimony launch takes (a longer queue is launched as it fills)
 MAX_PARS = 1000000000  # src/utilities.h
 ERROR_UNINITIALIZED_INSTANCE, ERROR_OUT_OF_RANGE, ERROR_NO_IMPLEMENTATION = -4, -5, -7
+ERROR_FLOATING_POINT = -8
+BRENT_IT_MAX = 1000  # kBrentItMax of phyml_amd/csrc/phyhip_brlen.hip (src/utilities.h:337)
+BRLEN_MAX_PATTERNS = 16384  # kBrlenMaxPatterns: phyhip_optimise_edge_length refuses instances of more patterns (built and tested up to here; not where it is faster)
+BRLEN_THREADS = {4: 1024, 20: 512}  # kBrlenThreads<S>: the one workgroup of the search kernel
+BRLEN_KEEP = {4: 3, 20: 1}  # kBrlenKeep<S>: rounds of a lane whose inputs stay in registers across the probes
 
 _lib = None
 
@@ -402,6 +408,20 @@ class Instance:
         lv = C.c_double(l); a = C.c_double(0); b = C.c_double(0)
         _chk(self.L.phyhip_calculate_eigen_lnl_dlnl(self.id, C.byref(lv), C.byref(a), C.byref(b)))
         return lv.value, a.value, b.value
+
+    def optimise_edge_length(self, l, init_lnl, iter_max=BRENT_IT_MAX, tol=1e-3):
+        """phyhip_optimise_edge_length: Br_Len_Spline on the products update_eigen_lr left, one device call.
+        Returns (l, lnL, dlnL, evaluations, status)."""
+        lv = C.c_double(l); a = C.c_double(0); b = C.c_double(0); n = C.c_int(0); st = C.c_int(0)
+        _chk(self.L.phyhip_optimise_edge_length(self.id, C.byref(lv), C.c_double(init_lnl), int(iter_max), C.c_double(tol),
+                                                C.byref(a), C.byref(b), C.byref(n), C.byref(st)))
+        return lv.value, a.value, b.value, n.value, st.value
+
+    def profile_read_edge_length(self):
+        """(kernel ms, calls, evaluations) of the edge-length searches since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0); ev = C.c_longlong(0)
+        _chk(self.L.phyhip_profile_read_edge_length(self.id, C.byref(ms), C.byref(n), C.byref(ev)))
+        return ms.value, n.value, ev.value
 
     def eigen_lnl(self, l):
         a = C.c_double(0)

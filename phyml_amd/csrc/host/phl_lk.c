@@ -9,7 +9,9 @@
  */
 #include "../../../include/phyhip_lk.h"
 #include "../../../include/phyhip.h"
+#include "../phyhip_brlen_step.h"
 
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -72,6 +74,8 @@ t_mod *Make_Model_Basic(int ns, int n_catg)
   m->l_min         = 1.E-8; /* src/init.c:711-714 */
   m->l_max         = 100.0;
   m->br_len_mult   = 1.0;
+  m->min_diff_lk_local = 1.E-03; /* src/init.c:770 */
+  m->brent_it_max      = BRENT_IT_MAX; /* :760 */
   for (int c = 0; c < n_catg; ++c)
   {
     m->gamma_rr[c]      = 1.0;
@@ -619,6 +623,103 @@ phydbl dLk(phydbl *l, t_edge *b, t_tree *tree)
   CHKV(phyhip_calculate_eigen_lnl_dlnl(tree->b_inst, l, &lnl, &dlnl), 0.0);
   tree->c_dlnL = dlnl;                                                     /* :749-750 */
   tree->c_lnL  = lnl;
+  return tree->c_lnL;
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* Br_Len_Opt (src/optimiz.c:607-663)                                                                   */
+/* ------------------------------------------------------------------------------------------------ */
+
+/* The search of Br_Len_Opt driven from the host: the steps of ../phyhip_brlen_step.h -- the very function the search kernel of
+   phyhip_optimise_edge_length runs -- with dLk() as the probe, one round trip each.  Returns that call's status word; *evals: the
+   dLk evaluations taken.  *l, tree->c_lnL, tree->c_dlnL end as the device call leaves them; tree->n_tot_bl_opt grows by one per step. */
+static int Br_Len_Search_On_Host(phydbl *l, t_edge *b, int n_iter_max, phydbl tol, t_tree *tree, int *evals)
+{
+  BrlenState st;
+  brlen_begin(&st, *l, tree->c_lnL, tol, tree->mod->l_min, tree->mod->l_max, n_iter_max, brlen_trip_cap(tree->mod->l_min, tree->mod->l_max));
+  Set_Use_Eigen_Lr(YES, tree);
+  while (!st.done)
+  {
+    phydbl x = st.l;
+    dLk(&x, b, tree); /* (clamps x where it stands) */
+    st.l = x;
+    brlen_step(&st, tree->c_lnL, tree->c_dlnL, 0);
+  }
+  *evals = st.evals;
+  *l = st.best_l;
+  tree->c_lnL  = st.best_lnL;
+  tree->c_dlnL = st.c_dlnL;
+  return st.status;
+}
+
+phydbl Br_Len_Opt(phydbl *l, t_edge *b, t_tree *tree)
+{
+  const t_mod *m = tree->mod;
+  Set_Update_Eigen_Lr(YES, tree);
+  Set_Use_Eigen_Lr(NO, tree);
+  const phydbl lk_begin = Lk(b, tree); /* (also leaves the edge's products on the device) */
+  Set_Update_Eigen_Lr(NO, tree);
+  Set_Use_Eigen_Lr(YES, tree);
+
+  const phydbl init_l = *l;
+  int status = 0, evals = 0;
+  tree->bl_opt_on_device = NO;
+  /* the route: the device call only where the caller asks for it (2).  Measured (profiles/brlen_opt.md) it beats the steps driven
+     from here on trees with many long searches alone -- one of thirteen measured shapes -- so it is not the default */
+  if (tree->bl_opt_host_chain == 2)
+  {
+    double lv = *l, lnl = 0.0, dlnl = 0.0;
+    const int rc = phyhip_optimise_edge_length(tree->b_inst, &lv, tree->c_lnL, m->brent_it_max, m->min_diff_lk_local, &lnl, &dlnl, &evals, &status);
+    if (rc == PHYHIP_SUCCESS)
+    {
+      tree->bl_opt_on_device = YES;
+      *l = lv;
+      tree->c_lnL  = lnl;
+      tree->c_dlnL = dlnl;
+    }
+    else if (rc != PHYHIP_ERROR_NO_IMPLEMENTATION)
+    {
+      Lk_Exit("phyhip_optimise_edge_length", phyhip_get_last_error());
+      return tree->c_lnL;
+    }
+  }
+  if (tree->bl_opt_on_device != YES) status = Br_Len_Search_On_Host(l, b, m->brent_it_max, m->min_diff_lk_local, tree, &evals);
+  /* tree->n_tot_bl_opt: every step of the search but the first probe counts, and the step that leaves [l_min, l_max] before its probe */
+  if (evals > 0) tree->n_tot_bl_opt += evals - 1 + (status == 1 || status == 2 || status == 7 ? 1 : 0);
+  tree->bl_opt_evaluations = evals;
+  tree->bl_opt_status      = status;
+  if (evals > 0)
+  {
+    int warn = 0;
+    CHKV(phyhip_get_numerical_warning(tree->b_inst, &warn), tree->c_lnL);
+    tree->numerical_warning = (short)(warn != 0);
+  }
+  if (status >= 3)
+  {
+    char msg[256];
+    if (status == 3) snprintf(msg, sizeof msg, "no acceptable root of the spline (l=%G init=%G)", *l, init_l);
+    else if (status == 4) snprintf(msg, sizeof msg, "the bracket u < v, dfu > 0, dfv < 0 does not hold (l=%G init=%G)", *l, init_l);
+    else if (status == 5) snprintf(msg, sizeof msg, "Too many iterations in edge length optimization routine (l=%G init=%G).", *l, init_l);
+    else if (status == 6) snprintf(msg, sizeof msg, "branch length is NaN");
+    else snprintf(msg, sizeof msg, "a bracket walk did not end within its trip bound (l=%G init=%G)", *l, init_l);
+    Set_Update_Eigen_Lr(NO, tree);
+    Set_Use_Eigen_Lr(NO, tree);
+    Lk_Exit("Br_Len_Spline", msg);
+    return tree->c_lnL;
+  }
+
+  b->l = *l;
+  Update_PMat_At_Given_Edge(b, tree);
+  Set_Update_Eigen_Lr(NO, tree);
+  Set_Use_Eigen_Lr(NO, tree);
+
+  const phydbl lk_end = tree->c_lnL;
+  if (lk_end < lk_begin - m->min_diff_lk_local)
+  { /* :656-661 */
+    char msg[128];
+    snprintf(msg, sizeof msg, "lk_beg = %f lk_end = %f", lk_begin, lk_end);
+    Lk_Exit("Br_Len_Opt", msg);
+  }
   return tree->c_lnL;
 }
 

@@ -1,5 +1,5 @@
 // phyhip_side.hpp -- the host layer of the units beside the hot path (phyhip_exact.hip, phyhip_ancestral.hip, phyhip_dist.hip,
-// phyhip_support.hip, phyhip_pars.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
+// phyhip_support.hip, phyhip_pars.hip, phyhip_brlen.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
 // by kind of instance, the kernel timer of a profiled instance, and what those units keep on the instance.  Host code only.
 #pragma once
 #include "phyhip_host.hpp"
@@ -193,6 +193,13 @@ struct SideUnits
     double    prof_ms = 0.0;     // while profiling: its kernels (phyhip_profile_read_support)
     int       prof_n = 0;
   } sup;
+  struct
+  { // phyhip_optimise_edge_length
+    void     *h_out = nullptr; // host-mapped: the record the search kernel writes (phyhip_brlen.hip, BrlenResult)
+    double    prof_ms = 0.0;   // while profiling: its kernel (phyhip_profile_read_edge_length)
+    int       prof_n = 0;
+    long long prof_evals = 0;  // ... and the evaluations its searches took
+  } brlen;
 };
 
 inline SideUnits &side_of(Instance *I)
@@ -205,6 +212,7 @@ inline void side_release(Instance *I) // phyhip_finalize_instance
 {
   if (!I->side) return;
   for (WorkSpace *w : {&I->side->exact.out, &I->side->anc.work, &I->side->dist.work, &I->side->sup.slots, &I->side->sup.work}) w->release();
+  if (I->side->brlen.h_out) (void)hipHostFree(I->side->brlen.h_out);
   delete I->side;
   I->side = nullptr;
 }

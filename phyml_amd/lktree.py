@@ -60,6 +60,19 @@ class t_tree_pars(t_tree):
                 ("step_mat", C.POINTER(C.c_int)), ("own_step_mat", C.c_short)]
 
 
+class t_mod_brlen(t_mod):
+    """t_mod with the fields Br_Len_Opt reads, appended behind use_m4mod: what Make_Model_Basic allocates (LkTree.s_opt casts)"""
+    _fields_ = [("min_diff_lk_local", C.c_double), ("brent_it_max", C.c_int)]
+
+
+class t_tree_brlen(C.Structure):
+    """... and t_tree with Br_Len_Opt's fields behind the parsimony ones: what the host layer's trees are.  One flat structure: the C
+    compiler packs n_tot_bl_opt into the tail padding behind own_step_mat, where a ctypes subclass would start behind it"""
+    _fields_ = t_tree._fields_ + t_tree_pars._fields_ + [
+        ("n_tot_bl_opt", C.c_int), ("bl_opt_evaluations", C.c_int), ("bl_opt_status", C.c_int),
+        ("bl_opt_host_chain", C.c_short), ("bl_opt_on_device", C.c_short)]
+
+
 _lib = None
 _errors = []
 
@@ -76,9 +89,9 @@ def load():
         if not os.path.exists(LK_LIB_PATH):
             raise capi.PhyhipError(f"{LK_LIB_PATH} not built: run __graft_entry__.build()")
         L = C.CDLL(LK_LIB_PATH)
-        L.Make_Tree_From_Edges.restype = C.POINTER(t_tree_pars)
+        L.Make_Tree_From_Edges.restype = C.POINTER(t_tree_brlen)
         L.Make_Model_Basic.restype = C.POINTER(t_mod)
-        for f in ("Lk", "dLk", "Br_Len_Newton", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk", "Statistics_To_SH", "Statistics_to_RELL"):
+        for f in ("Lk", "dLk", "Br_Len_Newton", "Br_Len_Opt", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk", "Statistics_To_SH", "Statistics_to_RELL"):
             getattr(L, f).restype = C.c_double
         # tests must survive the reference's print-and-Exit() convention
         L.Set_Exit_Handler(_exit_handler)
@@ -350,6 +363,36 @@ class LkTree:
         v = self.L.Br_Len_Newton(C.byref(lv), self.edge(b), self.tree)
         _raise_if_error()
         return lv.value, v
+
+    def Br_Len_Opt(self, b, force_host_chain=False, l=None, force_device=False):
+        """Br_Len_Opt(&b->l, b, tree) (src/optimiz.c:607): the edge's length optimised from its own value, or from `l`, which becomes
+        b->l first -- the search in one device call, or (force_host_chain, and wherever the call is not built for the instance) the same
+        search driving dLk() from the host.  By default the host layer drives dLk() (measured the faster route on all but one shape);
+        force_device takes the device call wherever it is built.  Returns (l, lnL, dlnL, evaluations, status); `on_device` says which route the search took."""
+        e = self.edge(b).contents
+        if l is not None:
+            e.l = float(l)
+        tr = self.tree.contents
+        tr.bl_opt_host_chain = 1 if force_host_chain else (2 if force_device else 0)
+        lp = C.cast(C.byref(e, t_edge.l.offset), C.POINTER(C.c_double))
+        v = self.L.Br_Len_Opt(lp, self.edge(b), self.tree)
+        tr.bl_opt_host_chain = 0
+        _raise_if_error()
+        return e.l, v, tr.c_dlnL, tr.bl_opt_evaluations, tr.bl_opt_status
+
+    @property
+    def s_opt(self):
+        """the model's min_diff_lk_local / brent_it_max (mod->s_opt in the reference), readable and writable"""
+        return C.cast(self.mod, C.POINTER(t_mod_brlen)).contents
+
+    @property
+    def on_device(self):
+        """whether the last Br_Len_Opt's search was the device call (phyhip_optimise_edge_length)"""
+        return bool(self.tree.contents.bl_opt_on_device)
+
+    @property
+    def n_tot_bl_opt(self):
+        return self.tree.contents.n_tot_bl_opt
 
     def Replay_Surface_Trace(self, trace):
         """trace: dict of equal-length arrays kind,a,b,c,d,e (int32) and x (float64); returns (out, out2)."""
