@@ -630,6 +630,64 @@ int phyhip_get_partial_parsimony(int instance, int bufferIndex, int *outUi, int 
    pattern x (operations + scored edges) since the previous read; reading resets all three.  Sharded: the slowest shard's time. */
 int phyhip_profile_read_parsimony(int instance, double *outKernelMs, int *outLaunches, double *outPatternUpdates);
 
+/* ---- regraft scan (src/spr.c: Test_One_Spr_Target) ------------------------------------------------------------------------------ */
+
+/* K regraft candidates of one pruned subtree in ONE call.  Candidate k joins three vectors that exist already: outLogLikelihoods[k] is
+   what phyhip_update_partials {destination a spare buffer, child 1 through the matrix of child1Length, child 2 through the matrix of
+   child2Length} followed by phyhip_calculate_edge_log_likelihoods {parent that spare buffer, child subtreePartials, the matrix of
+   subtreeLength} returns -- with PHYHIP_REGRAFT_SUBTREE_IS_LEFT the operands swap: the subtree is the parent operand and the computed
+   vector the child (subtreePartials must then be a partials buffer: a left side is never a tip in PhyML).  An index below tipCount
+   is a tip.  The three matrices of a candidate are built inside the call, into the unit's work space, from eigen system eigenIndex
+   with exactly the treatment phyhip_update_transition_matrices gives a length (MAX(0, l) x rate x br_len_mult, the clamp, the
+   SMALL_PIJ floor, the row renormalisation; the reference libm's exp): they are the reference's doubles, and so is the computed
+   vector (Exex / Exin / Inin by kind of child, the all-ones shortcut, patterns of weight <= DBL_MIN skipped, the children's
+   exponents added, the 2^256 rule under apply_lk_scaling).  The evaluation is Lk_Core's (the general product at every pattern,
+   Pull_Scaling_Factors, the category mix, Invariant_Lk's +I mix, the SMALL floor with its warning, the reference libm's log): the
+   reference's lnL to ~1e-13 relative, like phyhip_calculate_edge_log_likelihoods.  The bits of outLogLikelihoods[k] depend on
+   candidate k alone -- not on count, on k's place in the list or on how the call was cut into chunks (no floating-point atomics:
+   lane, wave, tile sums added in one fixed order).
+     State: queued matrix work and queued partial updates run first (the path updates of Test_One_Spr_Target_Recur, queued with
+   phyhip_update_partials, are seen); virtual buffers a candidate names are stored; then NOTHING of the instance changes but this
+   unit's work space -- every partial and scale vector, the matrix table, the per-site outputs, dot_prod and the numerical warning
+   stay as they were.  outWarnings[k] (may be NULL) is candidate k's own warning.  keepCandidate (-1: none) names one candidate whose
+   computed vector and scale vector are also kept in the work space for phyhip_get_regraft_partials; a caller that wants them in
+   a buffer uploads them (phyhip_set_partials / phyhip_set_scale_factors).  A plain call: the large-grid resident workgroups leave;
+   it waits for the stream and leaves it clean, so the Lk(b) / dLk calls that follow are served resident again.
+     Work space: 3 C S S doubles, one double per tile of 256 patterns and 72 bytes per candidate, next to the kept vector
+   (P C S doubles and P ints), grown on use, kept on the instance and bounded by phyhip_set_regraft_work_space (0: the default of
+   128 MiB); a list that needs more runs in chunks of candidates (at least one per chunk).  Identical lengths of a chunk are built
+   once.
+     One-process sharded instances: every shard scans its pattern range, the host adds each candidate's shard sums in shard order,
+   the kept vector is concatenated.  count == 0 succeeds and does nothing.  Not built (PHYHIP_ERROR_NO_IMPLEMENTATION): ranks of
+   phyhip_comm_init_rank, PHYHIP_FLAG_CLASS_AXIS and PHYHIP_FLAG_GENERIC_LOOP instances, states other than 4 / 20, MORE THAN 8
+   CATEGORIES (the 4-state kernel holds C x 4 values in registers; such instances are refused, not served), mixtures.
+   PHYHIP_ERROR_OUT_OF_RANGE: a buffer, tip or eigen index out of range, a tip as the left operand, keepCandidate >= count. */
+#define PHYHIP_REGRAFT_SUBTREE_IS_LEFT 1
+typedef struct
+{
+  int    child1Partials;   /* partials buffer or tip index: one side of the target edge        */
+  int    child2Partials;   /* ... the other side                                                */
+  int    subtreePartials;  /* the pruned subtree's vector: partials buffer or tip               */
+  int    flags;
+  double child1Length, child2Length, subtreeLength;  /* b->l->v of the two halves and of b_arrow */
+} phyhip_regraft_candidate;
+
+int phyhip_calculate_regraft_log_likelihoods(int instance, int eigenIndex, const phyhip_regraft_candidate *candidates,
+                                             int count, int keepCandidate, double *outLogLikelihoods, int *outWarnings);
+/* of keepCandidate of the last call: [pattern][category][state] and [pattern] (either may be NULL; rows of patterns without weight
+   are zero).  Before any call, or after one with keepCandidate -1: PHYHIP_ERROR_OUT_OF_RANGE */
+int phyhip_get_regraft_partials(int instance, double *outPartials, int *outScaleFactors);
+/* matrix `which` (0 child 1, 1 child 2, 2 subtree) of candidate `candidate` of the last call as the scan read it, [category][from][to].
+   A call that ran in chunks keeps the LAST chunk's matrices: an earlier candidate, a `which` outside 0..2 or a call before any scan:
+   PHYHIP_ERROR_OUT_OF_RANGE */
+int phyhip_get_regraft_transition_matrix(int instance, int candidate, int which, double *outMatrix);
+/* bound on the unit's work space in bytes (0: the default, 128 MiB) */
+int phyhip_set_regraft_work_space(int instance, long long maxBytes);
+/* while phyhip_profile(instance, 1): milliseconds of the matrix, scan and sum kernels (HIP events on the instance's stream; uploads
+   and downloads excluded; sharded: added over the shards), the calls and the candidates they served since the previous read;
+   reading resets all three */
+int phyhip_profile_read_regraft(int instance, double *outKernelMs, int *outCalls, long long *outCandidates);
+
 #ifdef __cplusplus
 }
 #endif

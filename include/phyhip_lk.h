@@ -184,6 +184,21 @@ void   Set_Update_Eigen_Lr(int yesno, t_tree *tree);
    stay with the caller. */
 phydbl Br_Len_Opt(phydbl *l, t_edge *b, t_tree *tree);
 phydbl Br_Len_Newton(phydbl *l, t_edge *b, t_tree *tree);
+/* The regraft scan of one pruned subtree in ONE device call (phyhip_calculate_regraft_log_likelihoods): what Test_One_Spr_Target
+   (src/spr.c:590-760) computes target by target -- the matrices of the two halves of the target edge and of b_arrow,
+   Update_Partial_Lk(b_arrow, n_link), Lk(b_arrow) -- for n target edges at once.  The subtree is the vector of b_sub on d_sub's
+   side (d_sub a tip: its tip vector) and hangs on a branch of length l_sub; candidate i joins the two side vectors of b_target[i]
+   through l_left[i] (the half on b_target[i]->left's side) and l_rght[i] (the right side is the tip where rght->tax); buffer
+   indices are resolved as Update_Partial_Lk / Lk resolve them.  link_is_left: n_link is b_arrow->left, so the joined vector is
+   Lk's left operand and the subtree the right one; NO: the subtree is the left operand (it must then be an internal node's vector).
+   lnL[i]: what Lk(b_arrow) would return for candidate i.  Updates queued with Update_Partial_Lk before the call (the path updates
+   of Test_One_Spr_Target_Recur, src/spr.c:543) are seen.  tree->c_lnL, every partial vector, the matrices of the edges and the
+   per-site outputs are left alone.
+   This layer has no Prune_Subtree / Graft_Subtree: on an INTACT tree the vectors are whatever the tree holds -- the side vectors of a
+   target edge still contain the subtree, so the numbers are those of the call sequence, not of a legal SPR move; a caller that has
+   pruned (or a recorded stream of a real search, tests/test_gpu_regraft.py) gets the search's candidates. */
+void Lk_Regraft_Scan(t_tree *tree, t_edge *b_sub, t_node *d_sub, int link_is_left, phydbl l_sub,
+                     int n, t_edge *const *b_target, const phydbl *l_left, const phydbl *l_rght, phydbl *lnL);
 /* host P-matrix (src/models.c:257-326, 353-373) -- used when tree->host_pmat == YES */
 void   PMat(phydbl l, const t_mod *mod, int pos, phydbl *Pij);
 

@@ -27,6 +27,12 @@ class Operation(C.Structure):
                 ("child2Partials", C.c_int), ("child2TransitionMatrix", C.c_int)]
 
 
+class RegraftCandidate(C.Structure):
+    """phyhip_regraft_candidate"""
+    _fields_ = [("child1Partials", C.c_int), ("child2Partials", C.c_int), ("subtreePartials", C.c_int), ("flags", C.c_int),
+                ("child1Length", C.c_double), ("child2Length", C.c_double), ("subtreeLength", C.c_double)]
+
+
 class InstanceDetails(C.Structure):
     _fields_ = [("resourceNumber", C.c_int), ("resourceName", C.c_char * 64), ("implName", C.c_char * 64),
                 ("flags", C.c_long), ("computeUnits", C.c_int), ("globalMemBytes", C.c_longlong)]
@@ -53,6 +59,8 @@ SYMBOLS = [
     "phyhip_set_parsimony", "phyhip_update_partial_parsimony", "phyhip_calculate_edge_parsimony", "phyhip_get_site_parsimony",
     "phyhip_get_partial_parsimony", "phyhip_profile_read_parsimony",
     "phyhip_optimise_edge_length", "phyhip_profile_read_edge_length",
+    "phyhip_calculate_regraft_log_likelihoods", "phyhip_get_regraft_partials", "phyhip_get_regraft_transition_matrix",
+    "phyhip_set_regraft_work_space", "phyhip_profile_read_regraft",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -63,6 +71,21 @@ PARS_STAGING = 4096  # kParsStaging: operations one parsimony launch takes (a lo
 MAX_PARS = 1000000000  # src/utilities.h
 ERROR_UNINITIALIZED_INSTANCE, ERROR_OUT_OF_RANGE, ERROR_NO_IMPLEMENTATION = -4, -5, -7
 ERROR_FLOATING_POINT = -8
+REGRAFT_SUBTREE_IS_LEFT = 1  # PHYHIP_REGRAFT_SUBTREE_IS_LEFT
+REGRAFT_TILE = 256  # kRegraftTile of phyml_amd/csrc/phyhip_regraft.hip: patterns per workgroup of the scan kernel
+REGRAFT_WORK_BYTES = 128 << 20  # kRegraftWorkBytes: the default bound on the scan's work space
+REGRAFT_MAX_CATEGORIES = 8  # kRegraftMaxCategories: instances of more categories are refused
+
+
+def regraft_chunk_candidates(P, C, S, max_bytes=REGRAFT_WORK_BYTES):
+    """candidates per chunk of regraft_log_likelihoods under a work-space bound, as include/phyhip.h states the layout: the kept
+    vector (P C S doubles, P ints rounded up to a multiple of 8 bytes), then per candidate 3 C S S doubles, a double per tile of
+    256 patterns and 72 bytes; at least one, at most 65535 (a grid's second dimension)"""
+    fixed = P * C * S * 8 + ((P + 1) // 2 * 2) * 4
+    per = 3 * C * S * S * 8 + (P + REGRAFT_TILE - 1) // REGRAFT_TILE * 8 + 72
+    return max(1, min(65535, (max_bytes - fixed) // per if max_bytes > fixed + per else 1))
+
+
 BRENT_IT_MAX = 1000  # kBrentItMax of phyml_amd/csrc/phyhip_brlen.hip (src/utilities.h:337)
 BRLEN_MAX_PATTERNS = 16384  # kBrlenMaxPatterns: phyhip_optimise_edge_length refuses instances of more patterns (built and tested up to here; not where it is faster)
 BRLEN_THREADS = {4: 1024, 20: 512}  # kBrlenThreads<S>: the one workgroup of the search kernel
@@ -422,6 +445,41 @@ class Instance:
         ms = C.c_double(0); n = C.c_int(0); ev = C.c_longlong(0)
         _chk(self.L.phyhip_profile_read_edge_length(self.id, C.byref(ms), C.byref(n), C.byref(ev)))
         return ms.value, n.value, ev.value
+
+    # -- regraft scan (src/spr.c: Test_One_Spr_Target)
+    def regraft_log_likelihoods(self, candidates, keep=-1, eigen_index=0, with_warnings=False):
+        """phyhip_calculate_regraft_log_likelihoods: candidates = iterable of (child1, child2, subtree, flags, child1 length,
+        child2 length, subtree length); keep: the candidate whose computed vector stays for regraft_partials().  Returns the
+        log-likelihoods [K], or (log-likelihoods, warnings [K]) with with_warnings."""
+        cand = list(candidates)
+        arr = (RegraftCandidate * max(1, len(cand)))()
+        for k, (c1, c2, sub, flags, l1, l2, l3) in enumerate(cand):
+            arr[k] = RegraftCandidate(int(c1), int(c2), int(sub), int(flags), float(l1), float(l2), float(l3))
+        out = np.zeros(len(cand)); w = np.zeros(len(cand), np.int32)
+        _chk(self.L.phyhip_calculate_regraft_log_likelihoods(self.id, int(eigen_index), arr, len(cand), int(keep), _ptr(out), _ptr(w)))
+        return (out, w) if with_warnings else out
+
+    def regraft_partials(self):
+        """phyhip_get_regraft_partials: (vector [P][C*S], scale exponents [P]) of the kept candidate of the last scan"""
+        v = np.zeros((self.P, self.C * self.S)); s = np.zeros(self.P, np.int32)
+        _chk(self.L.phyhip_get_regraft_partials(self.id, _ptr(v), _ptr(s)))
+        return v, s
+
+    def regraft_transition_matrix(self, candidate, which):
+        """phyhip_get_regraft_transition_matrix: matrix 0 (child 1), 1 (child 2) or 2 (subtree) of a candidate of the last scan"""
+        out = np.zeros((self.C, self.S, self.S))
+        _chk(self.L.phyhip_get_regraft_transition_matrix(self.id, int(candidate), int(which), _ptr(out)))
+        return out
+
+    def set_regraft_work_space(self, max_bytes):
+        """phyhip_set_regraft_work_space: the bound on the scan's work space in bytes (0: the default)"""
+        _chk(self.L.phyhip_set_regraft_work_space(self.id, C.c_longlong(int(max_bytes))))
+
+    def profile_read_regraft(self):
+        """(kernel ms, calls, candidates) of the regraft scans since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0); nc = C.c_longlong(0)
+        _chk(self.L.phyhip_profile_read_regraft(self.id, C.byref(ms), C.byref(n), C.byref(nc)))
+        return ms.value, n.value, nc.value
 
     def eigen_lnl(self, l):
         a = C.c_double(0)

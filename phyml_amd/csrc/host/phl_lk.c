@@ -607,6 +607,32 @@ phydbl Update_Lk_At_Given_Edge(t_edge *b_fcus, t_tree *tree)
   return tree->c_lnL;
 }
 
+/* Test_One_Spr_Target (src/spr.c:590-760) for n target edges in one device call; see include/phyhip_lk.h */
+void Lk_Regraft_Scan(t_tree *tree, t_edge *b_sub, t_node *d_sub, int link_is_left, phydbl l_sub,
+                     int n, t_edge *const *b_target, const phydbl *l_left, const phydbl *l_rght, phydbl *lnL)
+{
+  if (n <= 0) return;
+  if (d_sub != b_sub->left && d_sub != b_sub->rght) { Lk_Exit("Lk_Regraft_Scan", "d_sub is not an end of b_sub"); return; }
+  if (!link_is_left && d_sub->tax) { Lk_Exit("Lk_Regraft_Scan", "a tip cannot be the left operand"); return; }
+  phyhip_regraft_candidate *c = (phyhip_regraft_candidate *)calloc((size_t)n, sizeof *c);
+  if (!c) { Lk_Exit("Lk_Regraft_Scan", "out of memory"); return; }
+  const int sub = d_sub->tax ? d_sub->num : (d_sub == b_sub->left ? b_sub->p_lk_left_idx : b_sub->p_lk_rght_idx);
+  for (int i = 0; i < n; ++i)
+  {
+    const t_edge *b = b_target[i];
+    c[i].child1Partials  = b->left->tax ? b->left->num : b->p_lk_left_idx;  /* as Update_Eigen_Lr / Lk resolve the two sides */
+    c[i].child2Partials  = b->rght->tax ? b->p_lk_tip_idx : b->p_lk_rght_idx;
+    c[i].subtreePartials = sub;
+    c[i].flags           = link_is_left ? 0 : PHYHIP_REGRAFT_SUBTREE_IS_LEFT;
+    c[i].child1Length    = l_left[i];
+    c[i].child2Length    = l_rght[i];
+    c[i].subtreeLength   = l_sub;
+  }
+  const int rc = phyhip_calculate_regraft_log_likelihoods(tree->b_inst, 0, c, n, -1, lnL, NULL);
+  free(c);
+  if (rc < 0) Lk_Exit("phyhip_calculate_regraft_log_likelihoods", phyhip_get_last_error());
+}
+
 void Lk_Shard_Device(t_tree *tree, double *device_out)
 {
   t_edge *b = Traverse_For_Lk(tree);

@@ -15,7 +15,9 @@
 //                        entry points of its own)
 //   phyhip_pars.hip      parsimony scores, Update_Partial_Pars / Pars (Fitch and step-matrix kernels, a queue and entry points of its own)
 //   phyhip_brlen.hip     one edge's branch-length search, Br_Len_Opt / Br_Len_Spline (one one-workgroup kernel, entry points of its own)
-//   phyhip_side.hpp      the host layer those last six share (host code only): the work space grown on use, the walk over the plain
+//   phyhip_regraft.hip   the regraft scan of an SPR move: K candidates {two children, subtree, three lengths} in one call (matrix, scan
+//                        and sum kernels, entry points of its own)
+//   phyhip_side.hpp      the host layer those last seven share (host code only): the work space grown on use, the walk over the plain
 //                        instance or every shard, the refusals by kind of instance, the kernel timer, Instance::side
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --

@@ -1,5 +1,5 @@
 // phyhip_side.hpp -- the host layer of the units beside the hot path (phyhip_exact.hip, phyhip_ancestral.hip, phyhip_dist.hip,
-// phyhip_support.hip, phyhip_pars.hip, phyhip_brlen.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
+// phyhip_support.hip, phyhip_pars.hip, phyhip_brlen.hip, phyhip_regraft.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
 // by kind of instance, the kernel timer of a profiled instance, and what those units keep on the instance.  Host code only.
 #pragma once
 #include "phyhip_host.hpp"
@@ -159,6 +159,7 @@ struct SideTimer
 
 // ---- what the units keep on the instance (Instance::side, made on first use) ------------------------------------------------------
 constexpr size_t kDistBandBytes = 128u << 20; // pairwise distances: the raw counts of one band of taxa stay below this by default
+constexpr size_t kRegraftWorkBytes = kDistBandBytes; // regraft scan: the work space stays below this by default (a longer list runs in chunks)
 
 struct SideUnits
 {
@@ -200,6 +201,18 @@ struct SideUnits
     int       prof_n = 0;
     long long prof_evals = 0;  // ... and the evaluations its searches took
   } brlen;
+  struct
+  { // phyhip_calculate_regraft_log_likelihoods
+    WorkSpace work;                          // kept vector, its exponents, then one chunk's matrices, tile sums, sums, lengths, records, flags
+    size_t    max_bytes = kRegraftWorkBytes; // the bound on it (phyhip_set_regraft_work_space)
+    bool      valid = false;                 // a call has completed: the getters may read what it left
+    int       chunks = 0, last_first = 0;    // of the last call: its chunks, the first candidate of the last one
+    int       last_count = 0, last_keep = -1;
+    std::vector<int> last_slots;             // ... [candidate of the last chunk][3]: the matrix slots its record named
+    double    prof_ms = 0.0;                 // while profiling: its kernels (phyhip_profile_read_regraft)
+    int       prof_n = 0;
+    long long prof_cand = 0;                 // ... and the candidates they served
+  } regraft;
 };
 
 inline SideUnits &side_of(Instance *I)
@@ -211,7 +224,7 @@ inline SideUnits &side_of(Instance *I)
 inline void side_release(Instance *I) // phyhip_finalize_instance
 {
   if (!I->side) return;
-  for (WorkSpace *w : {&I->side->exact.out, &I->side->anc.work, &I->side->dist.work, &I->side->sup.slots, &I->side->sup.work}) w->release();
+  for (WorkSpace *w : {&I->side->exact.out, &I->side->anc.work, &I->side->dist.work, &I->side->sup.slots, &I->side->sup.work, &I->side->regraft.work}) w->release();
   if (I->side->brlen.h_out) (void)hipHostFree(I->side->brlen.h_out);
   delete I->side;
   I->side = nullptr;

@@ -380,6 +380,20 @@ class LkTree:
         _raise_if_error()
         return e.l, v, tr.c_dlnL, tr.bl_opt_evaluations, tr.bl_opt_status
 
+    def Regraft_Scan(self, b_sub, d_sub, link_is_left, l_sub, targets, l_left, l_rght):
+        """Lk_Regraft_Scan: the log-likelihoods [n] of regrafting the subtree of edge b_sub on node d_sub's side, on a branch of length
+        l_sub, onto each edge of `targets` cut into halves of l_left[i] / l_rght[i] -- one device call.  On an intact tree the
+        vectors are whatever the tree holds (include/phyhip_lk.h)."""
+        n = len(targets)
+        tg = (C.POINTER(t_edge) * max(1, n))(*[self.edge(int(b)) for b in targets])
+        ll = np.ascontiguousarray(l_left, dtype=np.float64); lr = np.ascontiguousarray(l_rght, dtype=np.float64)
+        assert ll.size == n and lr.size == n
+        out = np.zeros(n)
+        self.L.Lk_Regraft_Scan(self.tree, self.edge(int(b_sub)), self.node(int(d_sub)), 1 if link_is_left else 0, C.c_double(l_sub),
+                               n, tg, _dp(ll), _dp(lr), _dp(out))
+        _raise_if_error()
+        return out
+
     @property
     def s_opt(self):
         """the model's min_diff_lk_local / brent_it_max (mod->s_opt in the reference), readable and writable"""
