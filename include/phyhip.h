@@ -587,12 +587,26 @@ int phyhip_get_big_resident_stats(int instance, long long out[4]);
    minOperations says).  minOperations = 0 switches the feature off (and stores what
    is virtual); the default is 16, so the short launches of a tree search never leave anything virtual -- and the first of
    them that reads a virtual buffer stores them all, in its own launch.  Not on class-axis or generic-loop instances.  Sharded
-   instances: applied to every shard. */
+   instances: applied to every shard.
+     The same launches leave a second class of result unstored, "deferred": a result of any operation that every reader in the
+   launch takes from registers (the next two operations) and whose children are tips or buffers the launch leaves in memory.
+   Nothing is recomputed for it -- the operation runs at its place, only its store goes -- and its definition is that one
+   operation over stored inputs.  Everything above holds for it: the same readers store it first, the same snapshot slots keep its
+   matrices, the first short launch that reads one stores all of both classes, minOperations = 0 stores all of both classes and
+   stops deferring.  In addition a later launch that writes the buffer before reading it drops the definition (every repeated
+   whole-tree traversal does, for every deferred buffer: nothing is launched for it), and one that writes a buffer the definition
+   reads -- or phyhip_set_partials / phyhip_set_scale_factors on it -- stores the dependant first, on the old content (a short
+   launch that has to store one stores all of both classes with it, so that the short launches behind it keep their form). */
 int phyhip_set_virtual_buffers(int instance, int minOperations);
 
 /* out[0] buffers virtual right now, out[1] stores skipped so far (operations that left their result virtual), out[2] non-storing
    re-issues in front of readers, out[3] storing re-issues (materialisations).  Sharded instances: the first shard's counters. */
 int phyhip_get_virtual_stats(int instance, long long out[4]);
+
+/* The deferred class (phyhip_set_virtual_buffers): out[0] buffers deferred right now, out[1] stores deferred so far, out[2]
+   definitions stored on demand, out[3] definitions dropped because the buffer was written again first.  out[1] = out[0] + out[2] +
+   out[3].  None of them counts in phyhip_get_virtual_stats.  Sharded instances: the first shard's counters. */
+int phyhip_get_deferred_stats(int instance, long long out[4]);
 
 /* ---- parsimony (src/pars.c) --------------------------------------------------------------------------------------------------- */
 

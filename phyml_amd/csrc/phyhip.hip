@@ -367,6 +367,10 @@ static int build_instance(Instance *I, const hipDeviceProp_t &prop)
   I->virt.assign(I->nbuf, 0);
   I->keep_real_flag.assign(I->nbuf, 0);
   I->vdef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
+  // (deferred buffers need what virtual ones need: the two snapshot slots per internal buffer, the kernels with two-deep forwarding)
+  I->deferred.assign(I->nbuf, 0);
+  I->ddef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
+  I->defer_stores = I->nmat_all >= I->nmat + 2 * (I->nbuf - I->tips) && I->nbuf > I->tips;
   HIPCHK(hipMalloc((void **)&I->d_ops, (size_t)I->ops_slots * I->ops_slot_bytes));
   size_t chunk = std::max<size_t>(64 * 1024, std::max(I->ops_slot_bytes,
                                                        (size_t)I->C * I->S * I->S * sizeof(double) * 4));
@@ -591,6 +595,7 @@ int phyhip_set_partials(int instance, int bufferIndex, const double *inPartials)
   int rc = check_partial_index(I, bufferIndex, false);
   if (rc) return rc;
   devirtualise(I, bufferIndex); // (the scale vector of the last update stays what the reference has)
+  devirtualise_dependants(I, bufferIndex); // (deferred buffers computed from the old content are stored on it)
   rc = flush_sync(I);
   if (rc) return rc;
   if (!I->perm && !I->soa)
@@ -744,12 +749,16 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     if (idx[i] < 0 || idx[i] >= I->nmat) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "matrix index %d", idx[i]);
   bool queued_reader = false;
   for (int i = 0; i < count && !queued_reader; ++i) queued_reader = I->mat_in_queue[idx[i]] != 0;
-  // does a virtual buffer's definition read one of them?  (a scan of the buffer flags: only while some are virtual)
+  // does an unstored buffer's definition -- virtual or deferred -- read one of them?  (a scan of the buffer flags: only while there are some)
+  auto is_def = [&](int b) { return I->n_deferred > 0 && I->deferred[b] != 0; };
   auto depends = [&]() {
-    for (int b = I->tips; b < I->nbuf && I->n_virtual > 0; ++b)
-      if (I->virt[b])
+    for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
+      if (I->virt[b] || is_def(b))
+      {
+        const DevOp &d = I->virt[b] ? I->vdef[b] : I->ddef[b];
         for (int i = 0; i < count; ++i)
-          if (I->vdef[b].pm1 == idx[i] || I->vdef[b].pm2 == idx[i]) return true;
+          if (d.pm1 == idx[i] || d.pm2 == idx[i]) return true;
+      }
     return false;
   };
   // a queued operation still reads an old matrix -- or may read a virtual buffer through a definition that is about to move to
@@ -760,8 +769,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     int rc = flush(I, nullptr);
     if (rc) return rc;
   }
-  if (I->n_virtual == 0) return 0;
-  const unsigned long long stored_before = I->n_virt_material;
+  if (I->n_virtual == 0 && I->n_deferred == 0) return 0;
+  const unsigned long long stored_before = I->n_virt_material + I->n_def_material;
   // A virtual buffer is defined on the matrices as they are.  Before one changes: pmat_kernel / upload_matrices_kernel move the
   // old value into the buffer's own snapshot slot, and the definition reads it there from now on (a full traversal that follows
   // recomputes every buffer anyway; the host route rewrites a tree's matrices one call at a time) -- or the buffer is stored first.
@@ -780,10 +789,10 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
         if (idx[i] == pm) return i;
       return -1;
     };
-    for (int b = I->tips; b < I->nbuf && I->n_virtual > 0; ++b)
+    for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
     {
-      if (!I->virt[b]) continue;
-      DevOp &d = I->vdef[b];
+      if (!I->virt[b] && !is_def(b)) continue;
+      DevOp &d = I->virt[b] ? I->vdef[b] : I->ddef[b]; // (a deferred buffer's two snapshot slots are its own as well)
       const int  i1 = pos(d.pm1), i2 = pos(d.pm2);
       if (i1 < 0 && i2 < 0) continue;
       if (shadow->empty()) shadow->assign(count, -1);
@@ -796,8 +805,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     }
   }
   else
-    for (int i = 0; i < count && I->n_virtual > 0; ++i) devirtualise_matrix(I, idx[i]);
-  if (I->n_virt_material != stored_before)
+    for (int i = 0; i < count && (I->n_virtual > 0 || I->n_deferred > 0); ++i) devirtualise_matrix(I, idx[i]);
+  if (I->n_virt_material + I->n_def_material != stored_before)
   { // (stored on the old values: now)
     int rc = flush(I, nullptr);
     if (rc) return rc;
@@ -1144,6 +1153,7 @@ int phyhip_set_scale_factors(int instance, int bufferIndex, const int *in)
   int rc = check_partial_index(I, bufferIndex, false);
   if (rc) return rc;
   devirtualise(I, bufferIndex);
+  devirtualise_dependants(I, bufferIndex);
   if ((rc = flush_sync(I))) return rc;
   HIPCHK(hipMemcpy(I->d_scales + (size_t)(bufferIndex - I->tips) * scale_elems(I), in, I->P * sizeof(int), hipMemcpyHostToDevice));
   return PHYHIP_SUCCESS;
@@ -1310,7 +1320,7 @@ int phyhip_set_virtual_buffers(int instance, int minOperations)
   GET_INST(I, instance);
   if (minOperations < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "minOperations %d", minOperations);
   I->virt_min_ops = minOperations;
-  if (minOperations == 0 && I->n_virtual > 0)
+  if (minOperations == 0 && (I->n_virtual > 0 || I->n_deferred > 0))
   {
     devirtualise_all(I);
     return flush(I, nullptr);
@@ -1324,6 +1334,14 @@ int phyhip_get_virtual_stats(int instance, long long out[4])
   GET_INST_RES(I, instance);
   I_call.leave_query();
   out[0] = I->n_virtual; out[1] = (long long)I->n_virt_skipped; out[2] = (long long)I->n_virt_recomputed; out[3] = (long long)I->n_virt_material;
+  return PHYHIP_SUCCESS;
+}
+
+int phyhip_get_deferred_stats(int instance, long long out[4])
+{
+  if (Group *G = get_group(instance)) return phyhip_get_deferred_stats(G->sub_id[0], out);
+  GET_INST(I, instance); // (an ordinary entry: the resident-aware queries are a reviewed list, tests/test_abi.py)
+  out[0] = I->n_deferred; out[1] = (long long)I->n_def_skipped; out[2] = (long long)I->n_def_material; out[3] = (long long)I->n_def_dropped;
   return PHYHIP_SUCCESS;
 }
 

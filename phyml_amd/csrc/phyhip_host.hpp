@@ -314,6 +314,17 @@ struct Instance
   std::vector<unsigned char>             keep_real_flag;    // [nbuf]: buffer is in keep_real
   std::vector<int>                       keep_real;         // buffers the caller reads from MEMORY right after the next launch (devirtualise): that launch leaves them stored
   unsigned long long                     n_virt_skipped = 0, n_virt_recomputed = 0, n_virt_material = 0; // phyhip_get_virtual_stats
+  // Deferred buffers: the second class of unstored buffer.  A long list does not store a result that every
+  // reader in it takes from registers (the previous two operations') when its children are tips or buffers the launch leaves in
+  // memory: deferred[b] != 0, ddef[b] is the operation (one step over stored inputs, pad 0).  Whatever stores a virtual buffer
+  // stores a deferred one (devirtualise*); a later list that writes the buffer first drops the definition, one that reads it first
+  // or writes one of its inputs stores it in front (rewrite_pending).  Off in a hand-built Instance: phyhip_create_instance
+  // switches it on and sizes the vectors, and nothing indexes them before.
+  bool                                   defer_stores = false;
+  int                                    n_deferred = 0;
+  std::vector<unsigned char>             deferred;          // [nbuf]
+  std::vector<DevOp>                     ddef;              // [nbuf]
+  unsigned long long                     n_def_skipped = 0, n_def_material = 0, n_def_dropped = 0; // phyhip_get_deferred_stats
   std::vector<int>                       pm_idx;    // queued device-side matrix rebuilds (index, edge length)
   std::vector<double>                    pm_len;
   std::vector<int>                       pm_slot;   // matrix index -> position in pm_idx, or -1
@@ -575,6 +586,7 @@ void devirtualise(Instance *I, int buf);       // queue (in front) the storing o
 void devirtualise_all(Instance *I);
 void devirtualise_matrix(Instance *I, int m);  // ... for every virtual buffer whose definition reads matrix m
 void devirtualise_tip(Instance *I, int tip);   // ... reads tip row `tip`
+void devirtualise_dependants(Instance *I, int buf); // ... for every deferred buffer whose definition reads buffer `buf` (about to be written outside the queue)
 // snapshot slot w (0: the definition's first matrix, 1: its second) of internal buffer b in the matrix tables
 // (the launch in between has happened: nothing is asked to stay stored any more)
 inline void keep_real_clear(Instance *I)

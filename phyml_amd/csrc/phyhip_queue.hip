@@ -20,6 +20,18 @@ void devirtualise(Instance *I, int buf)
     I->keep_real_flag[buf] = 1;
     I->keep_real.push_back(buf);
   }
+  if (I->n_deferred > 0 && buf >= I->tips && buf < I->nbuf && I->deferred[buf])
+  { // a deferred buffer: its definition reads tips, matrices and buffers that are in memory and have not been written since
+    // (rewrite_pending stores or drops it before one is) -- in front of the queue as well
+    DevOp op = I->ddef[buf];
+    op.pad   = 0;
+    I->pending.insert(I->pending.begin(), op);
+    I->mat_in_queue[op.pm1] = 1; I->mat_in_queue[op.pm2] = 1;
+    I->deferred[buf] = 0;
+    --I->n_deferred;
+    ++I->n_def_material;
+    return;
+  }
   if (I->n_virtual == 0 || buf < I->tips || buf >= I->nbuf || !I->virt[buf]) return;
   DevOp op = I->vdef[buf];
   op.pad   = 0;
@@ -32,22 +44,106 @@ void devirtualise(Instance *I, int buf)
   ++I->n_virt_material;
 }
 
+// (both classes of unstored buffer: virtual and deferred)
+static inline bool unstored(const Instance *I, int b) { return I->virt[b] || (I->n_deferred > 0 && I->deferred[b]); }
+static inline const DevOp &unstored_def(const Instance *I, int b) { return I->virt[b] ? I->vdef[b] : I->ddef[b]; }
+
 void devirtualise_all(Instance *I)
 {
-  for (int b = I->tips; b < I->nbuf && I->n_virtual > 0; ++b)
-    if (I->virt[b]) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
+    if (unstored(I, b)) devirtualise(I, b);
 }
 
 void devirtualise_matrix(Instance *I, int m)
 {
-  for (int b = I->tips; b < I->nbuf && I->n_virtual > 0; ++b)
-    if (I->virt[b] && (I->vdef[b].pm1 == m || I->vdef[b].pm2 == m)) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
+    if (unstored(I, b) && (unstored_def(I, b).pm1 == m || unstored_def(I, b).pm2 == m)) devirtualise(I, b);
 }
 
 void devirtualise_tip(Instance *I, int tip)
 {
-  for (int b = I->tips; b < I->nbuf && I->n_virtual > 0; ++b)
-    if (I->virt[b] && (I->vdef[b].c1 == tip || I->vdef[b].c2 == tip)) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
+    if (unstored(I, b) && (unstored_def(I, b).c1 == tip || unstored_def(I, b).c2 == tip)) devirtualise(I, b);
+}
+
+// A buffer is about to be written by something that does not pass through the queue (a setter): deferred buffers whose
+// definitions read it are stored first, on its old value
+void devirtualise_dependants(Instance *I, int buf)
+{
+  if (buf < I->tips) return;
+  for (int b = I->tips; b < I->nbuf && I->n_deferred > 0; ++b)
+    if (I->deferred[b] && (I->ddef[b].c1 == buf || I->ddef[b].c2 == buf)) devirtualise(I, b);
+}
+
+// Deferred buffers left by earlier launches against the list that is about to run and its evaluation, in order.  The list reads
+// the buffer before it writes it: stored in front.  It writes the buffer first: the old definition is dead (every repeated
+// whole-tree traversal ends here for every deferred buffer: two scans of the list, nothing launched).  It does not write the buffer
+// but one of its inputs: stored in front, where the definition still reads the input's old value.  Returns whether it stored one
+// (a short launch then stores them all: it is a list now in any case, and the short launches behind it keep their form).
+static bool settle_deferred(Instance *I, const EdgeEval *ee)
+{
+  if (I->n_deferred == 0) return false;
+  const int        n0 = (int)I->pending.size(), never = n0 + 1;
+  std::vector<int> first_read(I->nbuf, never), first_write(I->nbuf, never);
+  for (int k = 0; k < n0; ++k)
+  {
+    const DevOp &o = I->pending[k];
+    for (int c : {o.c1, o.c2})
+      if (c >= I->tips && first_read[c] == never) first_read[c] = k;
+    if (first_write[o.dest] == never) first_write[o.dest] = k;
+  }
+  if (ee)
+    for (int c : {ee->parent, ee->child})
+      if (c >= I->tips && first_read[c] == never) first_read[c] = n0;
+  bool stored = false;
+  auto written = [&](int c) { return c >= I->tips && first_write[c] != never; };
+  for (int b = I->tips; b < I->nbuf && I->n_deferred > 0; ++b)
+  {
+    if (!I->deferred[b]) continue;
+    if (first_read[b] < first_write[b]) { stored = true; devirtualise(I, b); }
+    else if (first_write[b] != never) { I->deferred[b] = 0; --I->n_deferred; ++I->n_def_dropped; }
+    else if (written(I->ddef[b].c1) || written(I->ddef[b].c2)) { stored = true; devirtualise(I, b); } // (an input is written)
+  }
+  return stored;
+}
+
+// Deferred buffers, the rule (on the list as it will be launched, front to back): a storing operation whose destination is written
+// once in the list, read in it only by the next two operations -- exactly the reads child_descs forwards in registers -- and
+// neither read by the evaluation nor asked for from memory (keep_real) does not store, if each child is a tip or a buffer that is
+// in memory after this launch: not virtual, not computed in-step, not deferred, not written again behind the operation.  So every
+// deferred definition is ONE step over stored inputs: no recursion and no order among definitions.
+static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> &L)
+{
+  const int        n = (int)L.size();
+  std::vector<int> n_dest(I->nbuf, 0), last_write(I->nbuf, -1), last_read(I->nbuf, -1);
+  for (int k = 0; k < n; ++k)
+  {
+    const DevOp &o = L[k];
+    ++n_dest[o.dest];
+    last_write[o.dest] = k;
+    if (o.c1 >= I->tips && !(o.pad & kOpInl1)) last_read[o.c1] = k;
+    if (o.c2 >= I->tips && !(o.pad & kOpInl2)) last_read[o.c2] = k;
+  }
+  // (the padded re-run of an odd list's last operation: the result three positions back is no longer in registers)
+  const int pad_read1 = (n & 1) ? L[n - 1].c1 : -1, pad_read2 = (n & 1) ? L[n - 1].c2 : -1;
+  auto in_memory = [&](int c, bool in_step, int i) {
+    return c < I->tips || (!in_step && !I->virt[c] && !I->deferred[c] && last_write[c] < i);
+  };
+  for (int i = 0; i + 1 < n; ++i)
+  {
+    DevOp &o = L[i];
+    if ((o.pad & kOpNoStore) || n_dest[o.dest] != 1) continue;
+    if (last_read[o.dest] <= i || last_read[o.dest] > i + 2) continue; // (never read behind it, or read from memory)
+    if ((ee && (ee->parent == o.dest || ee->child == o.dest)) || I->keep_real_flag[o.dest]) continue;
+    if (!in_memory(o.c1, o.pad & kOpInl1, i) || !in_memory(o.c2, o.pad & kOpInl2, i)) continue;
+    if (i + 3 == n && (pad_read1 == o.dest || pad_read2 == o.dest)) continue; // (the odd-list rule, for this class)
+    I->ddef[o.dest] = o;
+    I->ddef[o.dest].pad = 0;
+    I->deferred[o.dest] = 1;
+    ++I->n_deferred;
+    ++I->n_def_skipped;
+    o.pad |= kOpNoStore;
+  }
 }
 
 // The queue as it will be launched.  Short lists (or kernels without two-deep forwarding): the first one that reads a virtual
@@ -59,7 +155,8 @@ void devirtualise_tip(Instance *I, int tip)
 void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
 {
   I->pending_inl.clear();
-  const int n0 = (int)I->pending.size();
+  const bool stored_deferred = settle_deferred(I, ee);
+  const int  n0 = (int)I->pending.size();
   // (only launches of the LIST form: one- and two-operation launches -- records in the kernel arguments, the resident evaluators --
   // run kernels without in-step children and without the second forwarding level's guarantees: a list must keep three
   // operations even if each of its tip x tip operations leaves its place)
@@ -70,7 +167,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
     for (const DevOp &o : I->pending) stay += !(o.c1 < I->tips && o.c2 < I->tips);
     virtualise = stay >= 3;
   }
-  if (!virtualise && I->n_virtual == 0) return;
+  if (!virtualise && I->n_virtual == 0 && I->n_deferred == 0) return;
   if (!virtualise)
   { // A short launch.  If it reads a virtual buffer, EVERY virtual buffer is stored now, in this one launch: the short launches
     // of a tree search (SPR candidates, Lk(b), Br_Len_Opt) come in long runs after a full traversal, and one list of tip x tip
@@ -79,7 +176,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
     bool reads = false;
     for (const DevOp &o : I->pending) reads = reads || (o.c1 >= I->tips && I->virt[o.c1]) || (o.c2 >= I->tips && I->virt[o.c2]);
     if (ee) reads = reads || (ee->parent >= I->tips && I->virt[ee->parent]) || (ee->child >= I->tips && I->virt[ee->child]);
-    if (reads) devirtualise_all(I);
+    if (reads || stored_deferred) devirtualise_all(I); // (deferred buffers go with them; and with one that settle_deferred had to store)
     // (a queued operation that WRITES a virtual buffer stores it: real again -- its old definition must never be stored over it)
     for (const DevOp &o : I->pending)
       if (I->virt[o.dest]) { I->virt[o.dest] = 0; --I->n_virtual; }
@@ -170,6 +267,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
       if (I->virt[d1.dest]) { I->virt[d1.dest] = 0; --I->n_virtual; ++I->n_virt_material; }
     }
   }
+  if (I->defer_stores) defer_forwarded(I, ee, L);
   I->pending.swap(L);
   if (any_inl) I->pending_inl.swap(LI);
 }
