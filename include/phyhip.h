@@ -674,7 +674,8 @@ int phyhip_profile_read_parsimony(int instance, double *outKernelMs, int *outLau
      One-process sharded instances: every shard scans its pattern range, the host adds each candidate's shard sums in shard order,
    the kept vector is concatenated.  count == 0 succeeds and does nothing.  Not built (PHYHIP_ERROR_NO_IMPLEMENTATION): ranks of
    phyhip_comm_init_rank, PHYHIP_FLAG_CLASS_AXIS and PHYHIP_FLAG_GENERIC_LOOP instances, states other than 4 / 20, MORE THAN 8
-   CATEGORIES (the 4-state kernel holds C x 4 values in registers; such instances are refused, not served), mixtures.
+   CATEGORIES (the 4-state kernel holds C x 4 values in registers; such instances are refused, not served).  A mixture's class
+   instances are scanned together by phyhip_calculate_mixture_regraft_log_likelihoods, below.
    PHYHIP_ERROR_OUT_OF_RANGE: a buffer, tip or eigen index out of range, a tip as the left operand, keepCandidate >= count. */
 #define PHYHIP_REGRAFT_SUBTREE_IS_LEFT 1
 typedef struct
@@ -701,6 +702,64 @@ int phyhip_set_regraft_work_space(int instance, long long maxBytes);
    and downloads excluded; sharded: added over the shards), the calls and the candidates they served since the previous read;
    reading resets all three */
 int phyhip_profile_read_regraft(int instance, double *outKernelMs, int *outCalls, long long *outCandidates);
+
+/* ---- regraft scan of a mixture (src/spr.c: Test_One_Spr_Target on a mixture tree: MIXT_Update_Partial_Lk, MIXT_Lk) -------------- */
+
+/* K regraft candidates of one pruned subtree over ALL class trees of a mixture in ONE call.  instances[count] are the class
+   instances (one category each, as phyhip_calculate_mixture_log_likelihood takes them; 1..64), eigenIndices[count] the eigen system
+   each class takes; classProba / rMatWeight / eFrqWeight [count] and the three sums are MIXT_Lk's coefficients.  The class trees
+   share topology and buffer numbering, so ONE record serves every class: a record's buffer and tip indices mean the same buffer in
+   every class instance, and its three lengths are the mixture tree's -- each class scales them by its own category rate and
+   br_len_mult and clamps with its own l_min / l_max, exactly as phyhip_update_transition_matrices does for that instance.
+   outLogLikelihoods[k] is what the per-candidate route returns: in every class instance phyhip_update_transition_matrices of the
+   three lengths and phyhip_update_partials {a spare buffer <- child 1, child 2}, then ONE phyhip_calculate_mixture_log_likelihood
+   over the class list {that spare buffer, subtreePartials, the third matrix} (PHYHIP_REGRAFT_SUBTREE_IS_LEFT: the operands swap).
+     Per class everything phyhip_calculate_regraft_log_likelihoods does for an instance of one category: the three matrices built
+   into the work space (the reference's doubles), the joined vector as AVX_Update_Partial_Lk would store it (the reference's doubles:
+   tips from the class instance's own tip data, the all-ones shortcut, patterns of weight <= DBL_MIN skipped, the children's
+   exponents added, the 2^256 rule), Lk_Core's product with the subtree: the class likelihood x_k and the exponent f_k its own edge
+   evaluation would leave in unscaled_site_lk_cat / fact_sum_scale.  Then the site loop of MIXT_Lk (src/mixt.c:1027-1142) in the
+   operation order of phyhip_calculate_mixture_log_likelihood: f_k > 1024 becomes 1023 and raises the candidate's warning, a class at
+   exactly 1024 drops out, site_lk += x * proba * r_w / r_sum * e_w / e_sum / sum_probas in class order, the +I share set with
+   phyhip_set_mixture_invariant_sites on the FIRST instance, the SMALL floor with the candidate's warning, the reference libm's log,
+   the FIRST instance's pattern weights; a pattern without weight adds nothing.  The reference's lnL to ~1e-13 relative.  The bits of
+   outLogLikelihoods[k] depend on candidate k and the class list alone -- not on candidateCount, on k's place in the list or on the
+   chunks (no floating-point atomics: lane, wave, tile sums added in one fixed order); another order of the classes is another sum.
+     State: in every class instance queued matrix work and queued partial updates run first and virtual buffers a record names are
+   stored, all of it before anything is launched; the kernels run on the first instance's stream; the call waits for it and leaves
+   every class stream clean (the large-grid resident workgroups leave; Lk(b) / dLk afterwards are served resident again).  NOTHING
+   of any instance changes but a work space kept on the FIRST instance, apart from the plain scan's own: partials, exponents, matrix
+   tables, site outputs, dot_prod and warning flags stay as they were.  outWarnings[k] (may be NULL) is candidate k's own warning.
+   keepCandidate (-1: none): that candidate's computed vector and exponents are kept for every class.
+     Work space: per candidate 3 S S doubles a class, one double per tile of 256 patterns and 72 bytes; next to them the kept vectors
+   (P S doubles and P ints a class) and the per-class table (128 bytes a class, uploaded with the records); grown on use, bounded by
+   phyhip_set_mixture_regraft_work_space (0: the default of 128 MiB); a longer list runs in chunks of at least one candidate.
+   Identical lengths of a chunk are built once per class.
+     Class instances that are one-process sharded instances of one shard layout: every shard scans its pattern range over its
+   sub-instances, the host adds each candidate's shard sums in shard order, the kept vectors are concatenated.  candidateCount == 0
+   succeeds and does nothing.  PHYHIP_ERROR_OUT_OF_RANGE: count outside 1..64, an instance with more than one category, differing
+   pattern counts, state counts, buffer layouts or devices, sharded and plain instances mixed, a bad buffer, tip or eigen index, a
+   tip as the left operand, keepCandidate >= candidateCount.  Not built (PHYHIP_ERROR_NO_IMPLEMENTATION): class-axis entries,
+   PHYHIP_FLAG_GENERIC_LOOP instances, ranks of phyhip_comm_init_rank, states other than 4 / 20. */
+int phyhip_calculate_mixture_regraft_log_likelihoods(const int *instances, int count, const int *eigenIndices,
+                                                     const phyhip_regraft_candidate *candidates, int candidateCount, int keepCandidate,
+                                                     const double *classProba, const double *rMatWeight, const double *eFrqWeight,
+                                                     double rMatWeightSum, double eFrqWeightSum, double sumProbas,
+                                                     double *outLogLikelihoods, int *outWarnings);
+/* of keepCandidate of the last call with this first instance, class classIndex: [pattern][state] and [pattern] (either may be NULL;
+   rows of patterns without weight are zero).  Before any call, after one with keepCandidate -1, or a class that is not there:
+   PHYHIP_ERROR_OUT_OF_RANGE */
+int phyhip_get_mixture_regraft_partials(int firstInstance, int classIndex, double *outPartials, int *outScaleFactors);
+/* matrix `which` (0 child 1, 1 child 2, 2 subtree) of class classIndex and candidate `candidate` of the last call as the scan read
+   it, [from][to].  A call that ran in chunks keeps the LAST chunk's matrices: an earlier candidate, a class or candidate that is not
+   there, a `which` outside 0..2 or a call before any scan: PHYHIP_ERROR_OUT_OF_RANGE */
+int phyhip_get_mixture_regraft_transition_matrix(int firstInstance, int classIndex, int candidate, int which, double *outMatrix);
+/* bound on the work space in bytes (0: the default, 128 MiB) */
+int phyhip_set_mixture_regraft_work_space(int firstInstance, long long maxBytes);
+/* while phyhip_profile(firstInstance, 1): milliseconds of the matrix, scan and sum kernels (HIP events on the first instance's
+   stream; uploads and downloads excluded; sharded: added over the shards), the calls and the candidates they served since the
+   previous read; reading resets all three */
+int phyhip_profile_read_mixture_regraft(int firstInstance, double *outKernelMs, int *outCalls, long long *outCandidates);
 
 #ifdef __cplusplus
 }

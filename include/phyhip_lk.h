@@ -199,6 +199,18 @@ phydbl Br_Len_Newton(phydbl *l, t_edge *b, t_tree *tree);
    pruned (or a recorded stream of a real search, tests/test_gpu_regraft.py) gets the search's candidates. */
 void Lk_Regraft_Scan(t_tree *tree, t_edge *b_sub, t_node *d_sub, int link_is_left, phydbl l_sub,
                      int n, t_edge *const *b_target, const phydbl *l_left, const phydbl *l_rght, phydbl *lnL);
+/* The same scan on a mixture tree, where Lk(b_arrow) dispatches to MIXT_Lk and Update_Partial_Lk to MIXT_Update_Partial_Lk: ONE device
+   call over all class trees (phyhip_calculate_mixture_regraft_log_likelihoods).  class_trees[n_classes] are the class trees (one
+   category each, as the mixture evaluations take them); class_proba / r_mat_weight / e_frq_weight [n_classes] and the three sums are
+   MIXT_Lk's coefficients (src/mixt.c:1048-1053).  b_sub, d_sub and b_target[i] are edges and nodes of the FIRST class tree: indices are
+   resolved there as Lk_Regraft_Scan resolves them -- the class trees share the numbering -- and every class tree's instance is
+   passed.  l_sub, l_left[i], l_rght[i] are the mixture tree's lengths: each class applies its own rate, br_len_mult and clamp.
+   lnL[i]: what MIXT_Lk(b_arrow) would return for candidate i.  Every class tree's c_lnL is left alone.  This layer has no mixture tree
+   type: the caller holds the list of class trees. */
+void MIXT_Lk_Regraft_Scan(t_tree *const *class_trees, int n_classes, const phydbl *class_proba, const phydbl *r_mat_weight,
+                          const phydbl *e_frq_weight, phydbl r_mat_weight_sum, phydbl e_frq_weight_sum, phydbl sum_probas,
+                          t_edge *b_sub, t_node *d_sub, int link_is_left, phydbl l_sub,
+                          int n, t_edge *const *b_target, const phydbl *l_left, const phydbl *l_rght, phydbl *lnL);
 /* host P-matrix (src/models.c:257-326, 353-373) -- used when tree->host_pmat == YES */
 void   PMat(phydbl l, const t_mod *mod, int pos, phydbl *Pij);
 

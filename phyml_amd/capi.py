@@ -61,6 +61,8 @@ SYMBOLS = [
     "phyhip_optimise_edge_length", "phyhip_profile_read_edge_length",
     "phyhip_calculate_regraft_log_likelihoods", "phyhip_get_regraft_partials", "phyhip_get_regraft_transition_matrix",
     "phyhip_set_regraft_work_space", "phyhip_profile_read_regraft",
+    "phyhip_calculate_mixture_regraft_log_likelihoods", "phyhip_get_mixture_regraft_partials",
+    "phyhip_get_mixture_regraft_transition_matrix", "phyhip_set_mixture_regraft_work_space", "phyhip_profile_read_mixture_regraft",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -83,6 +85,20 @@ def regraft_chunk_candidates(P, C, S, max_bytes=REGRAFT_WORK_BYTES):
     256 patterns and 72 bytes; at least one, at most 65535 (a grid's second dimension)"""
     fixed = P * C * S * 8 + ((P + 1) // 2 * 2) * 4
     per = 3 * C * S * S * 8 + (P + REGRAFT_TILE - 1) // REGRAFT_TILE * 8 + 72
+    return max(1, min(65535, (max_bytes - fixed) // per if max_bytes > fixed + per else 1))
+
+
+MIXTURE_REGRAFT_CLASS_BYTES = 128  # sizeof(MixRegraftClass): an entry of the mixture scan's per-class table
+MIXTURE_REGRAFT_HEAD_BYTES = 200  # sizeof(MixRegraftHead): the combination's sums and the +I share, in front of that table
+
+
+def mixture_regraft_chunk_candidates(P, classes, S, max_bytes=REGRAFT_WORK_BYTES):
+    """candidates per chunk of mixture_regraft_log_likelihoods under a work-space bound, as include/phyhip.h states the layout: per
+    class the kept vector (P S doubles, P ints rounded up to a multiple of 8 bytes) and 128 bytes of the per-class table, the 200
+    bytes in front of that table, then per candidate 3 S S doubles a class, a double per tile of 256 patterns and 72 bytes; at
+    least one, at most 65535"""
+    fixed = classes * (P * S * 8 + ((P + 1) // 2 * 2) * 4 + MIXTURE_REGRAFT_CLASS_BYTES) + MIXTURE_REGRAFT_HEAD_BYTES
+    per = 3 * classes * S * S * 8 + (P + REGRAFT_TILE - 1) // REGRAFT_TILE * 8 + 72
     return max(1, min(65535, (max_bytes - fixed) // per if max_bytes > fixed + per else 1))
 
 
@@ -475,6 +491,31 @@ class Instance:
         """phyhip_set_regraft_work_space: the bound on the scan's work space in bytes (0: the default)"""
         _chk(self.L.phyhip_set_regraft_work_space(self.id, C.c_longlong(int(max_bytes))))
 
+    # -- regraft scan of a mixture: what the FIRST class instance keeps (mixture_regraft_log_likelihoods below)
+    def mixture_regraft_partials(self, class_index):
+        """phyhip_get_mixture_regraft_partials: (vector [P][S], scale exponents [P]) of class class_index of the kept candidate of the
+        last mixture scan whose first instance this is"""
+        v = np.zeros((self.P, self.S)); s = np.zeros(self.P, dtype=np.int32)
+        _chk(self.L.phyhip_get_mixture_regraft_partials(self.id, int(class_index), _ptr(v), _ptr(s)))
+        return v, s
+
+    def mixture_regraft_transition_matrix(self, class_index, candidate, which):
+        """phyhip_get_mixture_regraft_transition_matrix: matrix 0 (child 1), 1 (child 2) or 2 (subtree) of a class and a candidate of
+        the last mixture scan"""
+        out = np.zeros((self.S, self.S))
+        _chk(self.L.phyhip_get_mixture_regraft_transition_matrix(self.id, int(class_index), int(candidate), int(which), _ptr(out)))
+        return out
+
+    def set_mixture_regraft_work_space(self, max_bytes):
+        """phyhip_set_mixture_regraft_work_space: the bound on the mixture scan's work space in bytes (0: the default)"""
+        _chk(self.L.phyhip_set_mixture_regraft_work_space(self.id, C.c_longlong(int(max_bytes))))
+
+    def profile_read_mixture_regraft(self):
+        """(kernel ms, calls, candidates) of the mixture regraft scans since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0); nc = C.c_longlong(0)
+        _chk(self.L.phyhip_profile_read_mixture_regraft(self.id, C.byref(ms), C.byref(n), C.byref(nc)))
+        return ms.value, n.value, nc.value
+
     def profile_read_regraft(self):
         """(kernel ms, calls, candidates) of the regraft scans since the previous read, while profile(1)"""
         ms = C.c_double(0); n = C.c_int(0); nc = C.c_longlong(0)
@@ -589,6 +630,26 @@ def mixture_log_likelihood(instance_ids, parents, children, matrices, proba, r_m
                                                    da(r_mat_weight), da(e_frq_weight), C.c_double(r_sum), C.c_double(e_sum),
                                                    C.c_double(sum_probas), C.byref(out)))
     return out.value
+
+
+def mixture_regraft_log_likelihoods(instance_ids, eigen_indices, candidates, proba, r_mat_weight, e_frq_weight, r_sum, e_sum, sum_probas,
+                                    keep=-1, with_warnings=False):
+    """phyhip_calculate_mixture_regraft_log_likelihoods: the candidates of Instance.regraft_log_likelihoods over the class instances of
+    a mixture (one category each) in one device call, combined as MIXT_Lk combines them.  eigen_indices: the eigen system of each
+    class (None: 0 everywhere).  Returns the log-likelihoods [K] (and the per-candidate warnings with with_warnings)."""
+    L = load()
+    n = len(instance_ids)
+    ia = lambda v: (C.c_int * max(1, len(v)))(*[int(x) for x in v])
+    da = lambda v: (C.c_double * max(1, len(v)))(*[float(x) for x in v])
+    cand = list(candidates)
+    arr = (RegraftCandidate * max(1, len(cand)))()
+    for k, (c1, c2, sub, flags, l1, l2, l3) in enumerate(cand):
+        arr[k] = RegraftCandidate(int(c1), int(c2), int(sub), int(flags), float(l1), float(l2), float(l3))
+    out = np.zeros(len(cand)); w = np.zeros(len(cand), dtype=np.int32)
+    _chk(L.phyhip_calculate_mixture_regraft_log_likelihoods(ia(instance_ids), n, ia([0] * n if eigen_indices is None else eigen_indices), arr,
+                                                            len(cand), int(keep), da(proba), da(r_mat_weight), da(e_frq_weight),
+                                                            C.c_double(r_sum), C.c_double(e_sum), C.c_double(sum_probas), _ptr(out), _ptr(w)))
+    return (out, w) if with_warnings else out
 
 
 def mixture_log_likelihood_classes(instance_ids, parents, children, matrices, proba, r_mat_weight, e_frq_weight, r_sum, e_sum, sum_probas):

@@ -633,6 +633,39 @@ void Lk_Regraft_Scan(t_tree *tree, t_edge *b_sub, t_node *d_sub, int link_is_lef
   if (rc < 0) Lk_Exit("phyhip_calculate_regraft_log_likelihoods", phyhip_get_last_error());
 }
 
+/* the same scan over the class trees of a mixture (MIXT_Update_Partial_Lk, MIXT_Lk) in one device call; see include/phyhip_lk.h */
+void MIXT_Lk_Regraft_Scan(t_tree *const *class_trees, int n_classes, const phydbl *class_proba, const phydbl *r_mat_weight,
+                          const phydbl *e_frq_weight, phydbl r_mat_weight_sum, phydbl e_frq_weight_sum, phydbl sum_probas,
+                          t_edge *b_sub, t_node *d_sub, int link_is_left, phydbl l_sub,
+                          int n, t_edge *const *b_target, const phydbl *l_left, const phydbl *l_rght, phydbl *lnL)
+{
+  if (n <= 0) return;
+  if (n_classes < 1 || n_classes > 64) { Lk_Exit("MIXT_Lk_Regraft_Scan", "1..64 class trees"); return; }
+  if (d_sub != b_sub->left && d_sub != b_sub->rght) { Lk_Exit("MIXT_Lk_Regraft_Scan", "d_sub is not an end of b_sub"); return; }
+  if (!link_is_left && d_sub->tax) { Lk_Exit("MIXT_Lk_Regraft_Scan", "a tip cannot be the left operand"); return; }
+  phyhip_regraft_candidate *c = (phyhip_regraft_candidate *)calloc((size_t)n, sizeof *c);
+  if (!c) { Lk_Exit("MIXT_Lk_Regraft_Scan", "out of memory"); return; }
+  int ids[64], eig[64];
+  for (int k = 0; k < n_classes; ++k) { ids[k] = class_trees[k]->b_inst; eig[k] = 0; }
+  /* indices resolved on the first class tree: the class trees share the numbering */
+  const int sub = d_sub->tax ? d_sub->num : (d_sub == b_sub->left ? b_sub->p_lk_left_idx : b_sub->p_lk_rght_idx);
+  for (int i = 0; i < n; ++i)
+  {
+    const t_edge *b = b_target[i];
+    c[i].child1Partials  = b->left->tax ? b->left->num : b->p_lk_left_idx;
+    c[i].child2Partials  = b->rght->tax ? b->p_lk_tip_idx : b->p_lk_rght_idx;
+    c[i].subtreePartials = sub;
+    c[i].flags           = link_is_left ? 0 : PHYHIP_REGRAFT_SUBTREE_IS_LEFT;
+    c[i].child1Length    = l_left[i];
+    c[i].child2Length    = l_rght[i];
+    c[i].subtreeLength   = l_sub;
+  }
+  const int rc = phyhip_calculate_mixture_regraft_log_likelihoods(ids, n_classes, eig, c, n, -1, class_proba, r_mat_weight, e_frq_weight,
+                                                                  r_mat_weight_sum, e_frq_weight_sum, sum_probas, lnL, NULL);
+  free(c);
+  if (rc < 0) Lk_Exit("phyhip_calculate_mixture_regraft_log_likelihoods", phyhip_get_last_error());
+}
+
 void Lk_Shard_Device(t_tree *tree, double *device_out)
 {
   t_edge *b = Traverse_For_Lk(tree);

@@ -24,6 +24,11 @@
 // the reference's to ~1e-13, the KEPT vector and the matrices are the reference's doubles (tests/test_gpu_regraft.py).
 // It writes a work space of its own: partials, scale vectors, the matrix table, site outputs, dot_prod and the warning flag of the
 // instance stay as they were.
+// Below it the same scan for a mixture: phyhip_calculate_mixture_regraft_log_likelihoods takes the class instances, and one kernel
+// loops over the classes and combines them as MIXT_Lk does (mixregraft_matrices_kernel, mixregraft_classes_kernel; their header
+// stands in front of them).  Operand fetch, joined vector, product and the matrix body are device functions both scans call.
+#include <memory>
+
 #include "phyhip_side.hpp"
 #include "phyhip_layout.hpp"
 #include "phyhip_log.hpp"
@@ -83,20 +88,20 @@ struct NoStore
   template <class T> __device__ __forceinline__ void operator()(T *, const T) const {}
 };
 
-template <int S> __global__ __launch_bounds__(256) void regraft_pmat_kernel(const RegraftPmatParams q)
+// PMat_Empirical of one (length, category) by one workgroup of 256: out[S][S] from the eigen system {U, V, R}
+template <int S>
+__device__ __forceinline__ void regraft_pmat_body(const double l, const double *__restrict__ U, const double *__restrict__ V,
+                                                  const double *__restrict__ R, const double rate, const double br_len_mult, const double l_min,
+                                                  const double l_max, double *__restrict__ out, double *expt, double *tmp, double *rsum)
 {
-  __shared__ double expt[S], tmp[S * S], rsum[S];
-  const int    m = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
-  if (m == 0 && c == 0)
-    for (int k = tid; k < q.n_flags; k += 256) q.flags[k] = 0;
-  const double l = q.lengths[m];
+  const int tid = threadIdx.x;
   if (tid < S)
   {
-    double len = (l > 0.0 ? l : 0.0) * q.rates[c]; // src/lk.c:2296
-    len *= q.br_len_mult;                          // :2297
-    if (len < q.l_min) len = q.l_min;              // :2299-2300
-    else if (len > q.l_max) len = q.l_max;
-    expt[tid] = dev_exp(q.R[tid] * len);           // src/models.c:275
+    double len = (l > 0.0 ? l : 0.0) * rate; // src/lk.c:2296
+    len *= br_len_mult;                      // :2297
+    if (len < l_min) len = l_min;            // :2299-2300
+    else if (len > l_max) len = l_max;
+    expt[tid] = dev_exp(R[tid] * len);       // src/models.c:275
   }
   __syncthreads();
   // acc = sum_k (U[i][k] * expt[k]) * V[k][j], ascending k with FMA (src/models.c:278-292), then the floor (:293)
@@ -105,7 +110,7 @@ template <int S> __global__ __launch_bounds__(256) void regraft_pmat_kernel(cons
     const int i = e / S, j = e % S;
     double    acc = 0.0;
 #pragma unroll
-    for (int k = 0; k < S; ++k) acc = __builtin_fma(q.U[i * S + k] * expt[k], q.V[k * S + j], acc);
+    for (int k = 0; k < S; ++k) acc = __builtin_fma(U[i * S + k] * expt[k], V[k * S + j], acc);
     tmp[e] = (acc < kSmallPij) ? kSmallPij : acc;
   }
   __syncthreads();
@@ -117,13 +122,23 @@ template <int S> __global__ __launch_bounds__(256) void regraft_pmat_kernel(cons
     rsum[tid] = sum;
   }
   __syncthreads();
-  double *out = q.mats + ((size_t)m * q.C + c) * S * S;
   for (int e = tid; e < S * S; e += 256) out[e] = tmp[e] / rsum[e / S]; // :298
 }
 
+template <int S> __global__ __launch_bounds__(256) void regraft_pmat_kernel(const RegraftPmatParams q)
+{
+  __shared__ double expt[S], tmp[S * S], rsum[S];
+  const int m = blockIdx.x, c = blockIdx.y;
+  if (m == 0 && c == 0)
+    for (int k = threadIdx.x; k < q.n_flags; k += 256) q.flags[k] = 0;
+  regraft_pmat_body<S>(q.lengths[m], q.U, q.V, q.R, q.rates[c], q.br_len_mult, q.l_min, q.l_max, q.mats + ((size_t)m * q.C + c) * S * S, expt, tmp,
+                       rsum);
+}
+
 // one operand of category c at pattern p: a tip's 0/1 vector from its allowed-state mask, or a partials buffer in the instance's layout
-template <int S, int L>
-__device__ __forceinline__ void regraft_operand(const RegraftParams &q, const int idx, const uint32_t mask, const long long p, const int c,
+// (Q: RegraftParams, or the class of a mixture scan as MixRegraftSrc names its buffers)
+template <int S, int L, class Q>
+__device__ __forceinline__ void regraft_operand(const Q &q, const int idx, const uint32_t mask, const long long p, const int c,
                                                 double (&x)[S])
 {
   if (idx < q.tips)
@@ -139,8 +154,8 @@ __device__ __forceinline__ void regraft_operand(const RegraftParams &q, const in
 }
 
 // the C*S values of one category before the scaling decision (src/avx.c:527-587)
-template <int S, int L>
-__device__ __forceinline__ void regraft_join(const RegraftParams &q, const RegraftRec &r, const uint32_t k1, const uint32_t k2, const long long p,
+template <int S, int L, class Q>
+__device__ __forceinline__ void regraft_join(const Q &q, const RegraftRec &r, const uint32_t k1, const uint32_t k2, const long long p,
                                              const int c, const double *__restrict__ M1, const double *__restrict__ M2, double (&o)[S])
 {
   double x1[S], x2[S];
@@ -163,6 +178,32 @@ __device__ __forceinline__ void regraft_join(const RegraftParams &q, const Regra
     }
     o[i] = ones ? 1.0 : a * b;
   }
+}
+
+// Lk_Core's product of one category (src/avx.c:130-148, 184-210): o the computed vector, y the subtree's, M3 the third matrix (rows:
+// the right-side state); with sub_left the subtree is the left operand
+template <int S>
+__device__ __forceinline__ double regraft_product(const double *__restrict__ M3, const double (&o)[S], const double (&y)[S], const double *pis,
+                                                  const bool sub_left)
+{
+  double lkc = 0.0;
+#pragma unroll
+  for (int b4 = 0; b4 < S / 4; ++b4)
+  {
+    double t[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+    {
+      const int k = b4 * 4 + kk;
+      double    a = 0.0;
+#pragma unroll
+      for (int i = 0; i < S; ++i) a = __builtin_fma(M3[k * S + i], sub_left ? y[i] : o[i], a);
+      t[kk] = a * ((sub_left ? o[k] : y[k]) * pis[k]);
+    }
+    const double nrm = (t[0] + t[2]) + (t[1] + t[3]);
+    lkc = (S == 4) ? nrm : lkc + nrm;
+  }
+  return lkc;
 }
 
 // One lane per pattern, one candidate per blockIdx.y (which operands are tips is the same for the whole workgroup).  4 states: the
@@ -286,23 +327,7 @@ template <int S, int L> __global__ __launch_bounds__(256) void regraft_scan_kern
     }
     if (r.sub >= q.tips) regraft_operand<S, L>(q, r.sub, k3, p, c, y);
     const double *__restrict__ M3 = Ms + (S == 20 ? 2 * SS : (2 * kRegraftMaxCategories + c) * SS); // rows: the right-side state
-    double lkc = 0.0;
-#pragma unroll
-    for (int b4 = 0; b4 < S / 4; ++b4)
-    {
-      double t[4];
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk)
-      {
-        const int k = b4 * 4 + kk;
-        double    a = 0.0;
-#pragma unroll
-        for (int i = 0; i < S; ++i) a = __builtin_fma(M3[k * S + i], sub_left ? y[i] : o[i], a);
-        t[kk] = a * ((sub_left ? o[k] : y[k]) * pis[k]);
-      }
-      const double nrm = (t[0] + t[2]) + (t[1] + t[3]);
-      lkc = (S == 4) ? nrm : lkc + nrm;
-    }
+    const double lkc = regraft_product<S>(M3, o, y, pis, sub_left);
     const double t = lkc * q.cat_w[c]; // src/lk.c:818
     site = site + t;
   };
@@ -346,6 +371,200 @@ __global__ __launch_bounds__(64) void regraft_sum_kernel(const double *__restric
   double sum = 0.0;
   for (int t = 0; t < tiles; ++t) sum += tile_sums[(size_t)k * tiles + t];
   out[k] = sum;
+}
+
+// ---- the scan of a mixture: the same K candidates over every class tree, combined as MIXT_Lk combines them -------------------------
+// A class is an instance of one category with its own eigen system, frequencies, rate and tip data; the class trees share topology
+// and buffer numbering, so one record serves all of them.  Per candidate and class the three matrices are built by
+//   mixregraft_matrices_kernel<S>   grid (distinct lengths of the chunk, classes): regraft_pmat_body with the class's own eigen system,
+//                                   rate, multiplier and clamp, read from the per-class table in the work space;
+//   mixregraft_classes_kernel<S,L>  grid (pattern tiles of 256, candidate), one lane per pattern, the classes in a loop inside the
+//                                   workgroup: the class's three matrices staged in LDS (3 S S doubles), its joined vector -- S values,
+//                                   one category -- in registers at both state counts, so the 2^256 decision needs no second pass;
+//                                   x_k = Lk_Core's product, f_k = the sum of the two sides' exponents; then the site loop of MIXT_Lk
+//                                   (src/mixt.c:1027-1142) in the operation order of mixture_combine_kernel, accumulated in registers:
+//                                   nothing per class and pattern goes to memory except the kept candidate's vectors.
+// regraft_sum_kernel adds the tile sums.  The per-class table {buffers, tip data, frequencies, eigen system, rate, clamp, the three
+// coefficients} is 128 bytes a class -- 8 KB at 64 classes, more than the kernel-argument segment holds -- and goes up with the records.
+struct MixRegraftClass
+{
+  const uint8_t  *tip_codes;
+  const uint32_t *code_masks;
+  const double   *partials;
+  const int      *scales;
+  const double   *pi, *U, *V, *R;
+  double          rate, br_len_mult, l_min, l_max;
+  double          proba, r_w, e_w;
+  int             apply_scaling, pad;
+};
+static_assert(sizeof(MixRegraftClass) == 128, "the per-class table's entry");
+
+// what the combination needs beside the classes: in the work space in front of the per-class table, not among the kernel's arguments
+// (the 20-state kernel has no scalar registers to hold them through the class loop)
+struct MixRegraftHead
+{
+  double       r_sum, e_sum, sum_probas, pinvar;
+  const short *invar;      // the +I share of phyhip_set_mixture_invariant_sites on the first instance, or NULL
+  double       pi_inv[20]; // frequencies of the invariant class
+};
+static_assert(sizeof(MixRegraftHead) == 200, "the head in front of the per-class table");
+
+struct MixRegraftPmatParams
+{
+  const double          *lengths; // [slot] raw edge lengths of the mixture tree
+  const MixRegraftClass *cls;     // [class]
+  double                *mats;    // [slot][class][S][S]
+  int                   *flags;   // [n_flags] the launch's warning flags: zeroed here
+  int                    n_cls, n_flags;
+};
+
+struct MixRegraftParams
+{
+  const MixRegraftClass *cls;       // [class]
+  const MixRegraftHead  *head;
+  const double          *wght;      // the FIRST instance's pattern weights
+  const RegraftRec      *recs;      // [candidate of the launch]
+  const double          *mats;      // [slot][class][S][S]
+  double                *tile_sums; // [candidate][tiles]; behind the launch's tile sums its warning flags, [candidate] ints
+  double                *keep;      // [class][P][S], host order: the kept candidate's vectors; behind them their exponents, [class][P rounded up to even] ints
+  long long              P, Ppad;
+  int                    n_cls, tips, keep_cand;
+};
+
+// what regraft_operand reads of one class
+struct MixRegraftSrc
+{
+  const double *partials;
+  long long     P, Ppad;
+  int           C, tips;
+};
+
+template <int S> __global__ __launch_bounds__(256) void mixregraft_matrices_kernel(const MixRegraftPmatParams q)
+{
+  __shared__ double expt[S], tmp[S * S], rsum[S];
+  const int m = blockIdx.x, k = blockIdx.y;
+  if (m == 0 && k == 0)
+    for (int i = threadIdx.x; i < q.n_flags; i += 256) q.flags[i] = 0;
+  const MixRegraftClass &c = q.cls[k];
+  regraft_pmat_body<S>(q.lengths[m], c.U, c.V, c.R, c.rate, c.br_len_mult, c.l_min, c.l_max, q.mats + ((size_t)m * q.n_cls + k) * S * S, expt, tmp,
+                       rsum);
+}
+
+template <int S, int L> __global__ __launch_bounds__(256) void mixregraft_classes_kernel(const MixRegraftParams q)
+{
+  constexpr int SS = S * S;
+  __shared__ double Ms[3 * SS], wsum[4], pis[S];
+  RegraftRec r;
+  if constexpr (S == 20)
+  { // read as lane values (a volatile load is no scalar load): as scalars, the address arithmetic of three operands -- 64-bit, hoisted
+    // out of the class loop -- takes more scalar registers than the 20-state kernel has, and they spill
+    const volatile int *rp = reinterpret_cast<const volatile int *>(q.recs + blockIdx.y);
+    r.c1 = rp[0]; r.c2 = rp[1]; r.sub = rp[2]; r.flags = rp[3]; r.m1 = rp[4]; r.m2 = rp[5]; r.m3 = rp[6]; r.pad = 0;
+  }
+  else
+    r = q.recs[blockIdx.y];
+  const long long p = (long long)blockIdx.x * kRegraftTile + threadIdx.x;
+  const bool      in = p < q.P;
+  const double    w = in ? q.wght[p] : 0.0;
+  const bool      act = in && w > kSmall; // src/mixt.c:998-1003: a pattern without weight is never evaluated
+  const bool       keep = q.keep_cand == (int)blockIdx.y;
+  const bool       sub_left = (r.flags & PHYHIP_REGRAFT_SUBTREE_IS_LEFT) != 0;
+  int *const       warn = reinterpret_cast<int *>(q.tile_sums + (size_t)gridDim.y * gridDim.x) + blockIdx.y;
+  const size_t     MS = (size_t)q.n_cls * SS;
+  const size_t     g1 = (size_t)r.m1 * MS, g2 = (size_t)r.m2 * MS, g3 = (size_t)r.m3 * MS;
+
+  double site_lk = 0.0;
+#pragma nounroll
+  for (int k = 0; k < q.n_cls; ++k)
+  {
+    const MixRegraftClass &c = q.cls[k];
+    __syncthreads(); // (the lanes of the class before have read its matrices)
+    for (int i = threadIdx.x; i < SS; i += 256)
+    {
+      Ms[i]          = q.mats[g1 + k * SS + i];
+      Ms[SS + i]     = q.mats[g2 + k * SS + i];
+      Ms[2 * SS + i] = q.mats[g3 + k * SS + i];
+    }
+    if (threadIdx.x < S) pis[threadIdx.x] = c.pi[threadIdx.x];
+    __syncthreads();
+    double *const kv = q.keep + (size_t)k * q.P * S;
+    int *const    ke = reinterpret_cast<int *>(q.keep + (size_t)q.n_cls * q.P * S) + (size_t)k * (((size_t)q.P + 1) & ~(size_t)1);
+    if (!act)
+    { // the reference leaves such a pattern's entries as they were; here they are zero
+      if (in && keep)
+      {
+        for (int e = 0; e < S; ++e) kv[(size_t)p * S + e] = 0.0;
+        ke[p] = 0;
+      }
+      continue;
+    }
+    const MixRegraftSrc src{c.partials, q.P, q.Ppad, 1, q.tips};
+    uint32_t k1 = 0, k2 = 0, k3 = 0;
+    int      sc = 0, s3 = 0;
+    if (r.c1 < q.tips) k1 = tip_state_mask<S>(c.tip_codes, c.code_masks, q.Ppad, r.c1, p);
+    else sc += c.scales[(size_t)(r.c1 - q.tips) * q.Ppad + p];
+    if (r.c2 < q.tips) k2 = tip_state_mask<S>(c.tip_codes, c.code_masks, q.Ppad, r.c2, p);
+    else sc += c.scales[(size_t)(r.c2 - q.tips) * q.Ppad + p]; // src/avx.c:462-464
+    if (r.sub < q.tips) k3 = tip_state_mask<S>(c.tip_codes, c.code_masks, q.Ppad, r.sub, p);
+    else s3 = c.scales[(size_t)(r.sub - q.tips) * q.Ppad + p];
+
+    // the class's joined vector, as AVX_Update_Partial_Lk would store it: one pass, the S values wait in registers for the decision
+    double o[S];
+    regraft_join<S, L>(src, r, k1, k2, p, 0, Ms, Ms + SS, o);
+    double mx = -__builtin_huge_val(); // (src/avx.c:497-502; `>`: a NaN never becomes the maximum)
+#pragma unroll
+    for (int i = 0; i < S; ++i) mx = (o[i] > mx) ? o[i] : mx;
+    if (mx < kInvTwoToLarge && c.apply_scaling)
+    { // src/avx.c:504-510; multiplication by 2^256 is exact
+#pragma unroll
+      for (int i = 0; i < S; ++i) o[i] *= kTwoToLarge;
+      sc += kLarge;
+    }
+    if (keep)
+    {
+#pragma unroll
+      for (int i = 0; i < S; ++i) kv[(size_t)p * S + i] = o[i];
+      ke[p] = sc;
+    }
+    double y[S];
+    regraft_operand<S, L>(src, r.sub, k3, p, 0, y);
+    // the site loop of MIXT_Lk, as mixture_combine_kernel has it (src/mixt.c:1027-1053).  (The exponent's cap with its store stands in
+    // front of the product: behind it the compiler moves the product's arithmetic, but not its 400 loads, across the store -- and spills)
+    int f = c.apply_scaling ? sc + s3 : 0; // the class's fact_sum_scale
+    if (f > 1024)
+    {
+      f = 1023;
+      *warn = 1;
+    }
+    const double x = regraft_product<S>(Ms + 2 * SS, o, y, pis, sub_left); // ... and its unscaled_site_lk_cat
+    const double u = mix_unscale(x, f);
+    site_lk += u * c.proba * c.r_w / q.head->r_sum * c.e_w / q.head->e_sum / q.head->sum_probas;
+  }
+
+  double contrib = 0.0;
+  if (act)
+  {
+    const MixRegraftHead &h = *q.head;
+    if (h.invar)
+    { // src/mixt.c:1086-1116: Invariant_Lk of the invariant class at scale 2^0, then the mixing
+      const int    iv = h.invar[p];
+      const double inv = iv >= 0 ? h.pi_inv[iv] : 0.0;
+      site_lk = site_lk * (1. - h.pinvar) + inv * h.pinvar;
+    }
+    if (site_lk < kSmall)
+    {
+      site_lk = kSmall;
+      *warn = 1;
+    }
+    contrib = w * phyhip_log_ref(site_lk, phyhip_log_data); // src/mixt.c:1133
+  }
+
+  // the wave's fixed shuffle tree, then the waves in wave order
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) contrib += __shfl_down(contrib, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = contrib;
+  __syncthreads();
+  if (threadIdx.x == 0) q.tile_sums[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
 // bytes of the work space one candidate of a chunk takes (its three matrices, tile sums, record, lengths, sum and flag) ...
@@ -487,6 +706,199 @@ static int regraft_run(Instance *I, int eigen, const phyhip_regraft_candidate *c
   return PHYHIP_SUCCESS;
 }
 
+// ---- the mixture scan's host side ----------------------------------------------------------------------------------------------------
+static size_t mixregraft_exponent_ints(const Instance *I) { return ((size_t)I->P + 1) & ~(size_t)1; }
+// bytes of the work space one candidate of a chunk takes over n classes ...
+static size_t mixregraft_candidate_bytes(const Instance *I, int n)
+{
+  const size_t tiles = (size_t)((I->P + kRegraftTile - 1) / kRegraftTile);
+  return 3 * (size_t)n * I->S * I->S * sizeof(double) + tiles * sizeof(double) + sizeof(RegraftRec) + 3 * sizeof(double) + sizeof(double) + 8;
+}
+// ... and of the kept vectors with their exponents and the per-class table, which every call's layout reserves
+static size_t mixregraft_keep_bytes(const Instance *I, int n) { return (size_t)n * ((size_t)I->P * I->S * sizeof(double) + mixregraft_exponent_ints(I) * sizeof(int)); }
+static size_t mixregraft_table_bytes(int n) { return sizeof(MixRegraftHead) + (size_t)n * sizeof(MixRegraftClass); } // (the head in front of the table)
+static size_t mixregraft_fixed_bytes(const Instance *I, int n) { return mixregraft_keep_bytes(I, n) + mixregraft_table_bytes(n); }
+
+struct MixRegraftCoef
+{
+  const double *proba, *r_w, *e_w;
+  double        r_sum, e_sum, sum_probas;
+};
+
+// The class instances of one mixture (plain instances: the classes themselves, or one shard of each): their patterns of every
+// candidate.  sums[k] / warns[k] receive this list's share.
+static int mixregraft_run(const int *ids, int n_cls, const int *eigen, const phyhip_regraft_candidate *cand, int count, int keep,
+                          const MixRegraftCoef &co, double *sums, int *warns)
+{
+  static const char *const who = "phyhip_calculate_mixture_regraft_log_likelihoods";
+  int rc;
+  std::vector<std::unique_ptr<Entered<false>>> entered; // (kSideCall: the large-grid resident workgroups of every class leave)
+  std::vector<Instance *>                      cls;
+  for (int k = 0; k < n_cls; ++k)
+  {
+    entered.emplace_back(new Entered<false>(ids[k]));
+    if (entered.back()->rc()) return entered.back()->rc();
+    cls.push_back(entered.back()->inst());
+  }
+  Instance *const I0 = cls[0];
+  const int       layout = layout_of(I0);
+  for (int k = 0; k < n_cls; ++k)
+  {
+    const Instance *I = cls[k];
+    if ((rc = refuse_kind(I, who, kRefuseRank | kRefuseClassAxis | kRefuseGenericLoop | kRefuseStates))) return rc;
+    if (I->C != 1) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d has %d categories (a class instance has one)", who, k, I->C);
+    if (I->P != I0->P || I->Ppad != I0->Ppad || I->S != I0->S || I->dev != I0->dev || I->tips != I0->tips || I->nbuf != I0->nbuf ||
+        layout_of(I) != layout)
+      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d: another pattern count, state count, buffer layout or device than class 0", who, k);
+    if (eigen[k] < 0 || eigen[k] >= I->NE) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d: eigenIndex %d (0..%d)", who, k, eigen[k], I->NE - 1);
+  }
+  for (int k = 0; k < count; ++k)
+  {
+    const phyhip_regraft_candidate &c = cand[k];
+    if ((rc = check_partial_index(I0, c.child1Partials, true)) || (rc = check_partial_index(I0, c.child2Partials, true)) ||
+        (rc = check_partial_index(I0, c.subtreePartials, true)))
+      return fail(rc, "%s: candidate %d: %s", who, k, std::string(g_err).c_str());
+    if ((c.flags & PHYHIP_REGRAFT_SUBTREE_IS_LEFT) && c.subtreePartials < I0->tips)
+      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d: tip %d as the left operand", who, k, c.subtreePartials);
+  }
+  auto &U = side_of(I0).mixregraft;
+  U.valid = false;
+  // every class: the buffers a record names stored, queued matrix work and partial updates run (the path updates of the caller are
+  // seen), its stream drained -- all of it before anything is launched
+  for (Instance *I : cls)
+  {
+    for (int k = 0; k < count; ++k)
+    {
+      devirtualise(I, cand[k].child1Partials); devirtualise(I, cand[k].child2Partials); devirtualise(I, cand[k].subtreePartials);
+    }
+    if ((rc = flush_sync(I))) return rc;
+    if ((rc = upload_masks(I))) return rc;
+  }
+
+  const size_t SS = (size_t)I0->S * I0->S, MS = (size_t)n_cls * SS, tiles = (size_t)((I0->P + kRegraftTile - 1) / kRegraftTile);
+  const size_t per = mixregraft_candidate_bytes(I0, n_cls), fixed = mixregraft_fixed_bytes(I0, n_cls);
+  size_t       chunk = U.max_bytes > fixed + per ? (U.max_bytes - fixed) / per : 1;
+  chunk = std::min(chunk, std::min((size_t)count, (size_t)65535)); // (a grid's second dimension holds 65535 candidates)
+  if ((rc = U.work.reserve(fixed + chunk * per, who))) return rc;
+  // layout: kept vectors | their exponents | matrices | of a launch of n: tile sums, flags (8 bytes per candidate), sums | class table,
+  // records, lengths (what goes up is one copy, what comes down is one copy)
+  MixRegraftParams q;
+  memset(&q, 0, sizeof q);
+  q.keep = (double *)U.work.ptr;
+  double *d_mats = (double *)((char *)U.work.ptr + mixregraft_keep_bytes(I0, n_cls));
+  q.mats = d_mats;
+  q.tile_sums = d_mats + 3 * chunk * MS;
+  MixRegraftHead  *d_head = (MixRegraftHead *)(q.tile_sums + chunk * tiles + 2 * chunk);
+  MixRegraftClass *d_cls = (MixRegraftClass *)(d_head + 1);
+  RegraftRec      *d_recs = (RegraftRec *)(d_cls + n_cls);
+  q.head = d_head; q.cls = d_cls; q.recs = d_recs;
+  q.wght = I0->d_wght;
+  q.P = I0->P; q.Ppad = I0->Ppad; q.n_cls = n_cls; q.tips = I0->tips;
+  MixRegraftHead head;
+  memset(&head, 0, sizeof head);
+  head.r_sum = co.r_sum; head.e_sum = co.e_sum; head.sum_probas = co.sum_probas;
+  head.invar = I0->mix_invar_model ? I0->d_invar : nullptr; head.pinvar = I0->mix_pinvar;
+  for (int s = 0; s < 20; ++s) head.pi_inv[s] = I0->mix_pi_inv[s];
+  std::vector<MixRegraftClass> table((size_t)n_cls);
+  for (int k = 0; k < n_cls; ++k)
+  {
+    const Instance  *I = cls[k];
+    MixRegraftClass &t = table[k];
+    memset(&t, 0, sizeof t);
+    t.tip_codes = I->d_tipcodes; t.code_masks = I->d_masks; t.partials = I->d_partials; t.scales = I->d_scales; t.pi = I->d_pi;
+    t.U = I->d_evec + (size_t)eigen[k] * SS; t.V = I->d_ivec + (size_t)eigen[k] * SS; t.R = I->d_eval + (size_t)eigen[k] * I->S;
+    t.rate = I->h_rates[0]; t.br_len_mult = I->br_len_mult; t.l_min = I->l_min; t.l_max = I->l_max;
+    t.proba = co.proba[k]; t.r_w = co.r_w[k]; t.e_w = co.e_w[k];
+    t.apply_scaling = I->apply_scaling;
+  }
+  MixRegraftPmatParams pq;
+  memset(&pq, 0, sizeof pq);
+  pq.mats = d_mats; pq.cls = d_cls; pq.n_cls = n_cls;
+
+  std::vector<RegraftRec> recs;
+  std::vector<double>     lens;
+  std::vector<char>       up;
+  std::vector<double>     down;
+  std::unordered_map<unsigned long long, int> slot_of; // a length's bits -> its matrix slot: identical lengths of a chunk are built once per class
+  auto slot = [&](double l) {
+    unsigned long long bits;
+    memcpy(&bits, &l, sizeof bits);
+    const auto it = slot_of.find(bits);
+    if (it != slot_of.end()) return it->second;
+    lens.push_back(l);
+    return slot_of[bits] = (int)lens.size() - 1;
+  };
+  SideTimer tm(I0);
+  U.chunks = 0;
+  const size_t tb = mixregraft_table_bytes(n_cls);
+  for (size_t first = 0; first < (size_t)count; first += chunk)
+  {
+    const size_t n = std::min(chunk, (size_t)count - first);
+    recs.clear(); lens.clear(); slot_of.clear();
+    for (size_t k = 0; k < n; ++k)
+    {
+      const phyhip_regraft_candidate &c = cand[first + k];
+      recs.push_back(RegraftRec{c.child1Partials, c.child2Partials, c.subtreePartials, c.flags, slot(c.child1Length), slot(c.child2Length),
+                                slot(c.subtreeLength), 0});
+    }
+    up.resize(tb + n * sizeof(RegraftRec) + lens.size() * sizeof(double));
+    memcpy(up.data(), &head, sizeof head);
+    memcpy(up.data() + sizeof head, table.data(), (size_t)n_cls * sizeof(MixRegraftClass));
+    memcpy(up.data() + tb, recs.data(), n * sizeof(RegraftRec));
+    memcpy(up.data() + tb + n * sizeof(RegraftRec), lens.data(), lens.size() * sizeof(double));
+    HIPCHK(hipMemcpyAsync(d_head, up.data(), up.size(), hipMemcpyHostToDevice, I0->stream));
+    pq.lengths = (const double *)(d_recs + n);
+    double *const d_down = q.tile_sums + n * tiles; // (where the scan kernel of a launch of n candidates looks for its flags)
+    double *const d_out = d_down + n;
+    pq.flags = (int *)d_down; pq.n_flags = (int)n;
+    q.keep_cand = (keep >= (int)first && keep < (int)(first + n)) ? keep - (int)first : -1;
+    if ((rc = tm.tic())) return rc;
+    const dim3 pgrid((unsigned)lens.size(), (unsigned)n_cls), sgrid((unsigned)tiles, (unsigned)n), block(256);
+    if (I0->S == 4)
+    {
+      hipLaunchKernelGGL(mixregraft_matrices_kernel<4>, pgrid, block, 0, I0->stream, pq);
+      if (layout == 2) hipLaunchKernelGGL((mixregraft_classes_kernel<4, 2>), sgrid, block, 0, I0->stream, q);
+      else hipLaunchKernelGGL((mixregraft_classes_kernel<4, 0>), sgrid, block, 0, I0->stream, q);
+    }
+    else
+    {
+      hipLaunchKernelGGL(mixregraft_matrices_kernel<20>, pgrid, block, 0, I0->stream, pq);
+      if (layout == 1) hipLaunchKernelGGL((mixregraft_classes_kernel<20, 1>), sgrid, block, 0, I0->stream, q);
+      else hipLaunchKernelGGL((mixregraft_classes_kernel<20, 0>), sgrid, block, 0, I0->stream, q);
+    }
+    hipLaunchKernelGGL(regraft_sum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, I0->stream, (const double *)q.tile_sums, d_out, (int)tiles,
+                       (int)n);
+    HIPCHK(hipGetLastError());
+    if ((rc = tm.mark())) return rc;
+    HIPCHK(hipStreamSynchronize(I0->stream));
+    if ((rc = tm.toc(U.prof_ms))) return rc;
+    down.resize(2 * n);
+    HIPCHK(hipMemcpy(down.data(), d_down, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
+    memcpy(sums + first, down.data() + n, n * sizeof(double));
+    for (size_t k = 0; k < n; ++k) warns[first + k] = reinterpret_cast<const int *>(down.data())[k] ? 1 : 0;
+    ++U.chunks;
+    U.last_first = (int)first;
+  }
+  // the last chunk's matrices stay in the work space for phyhip_get_mixture_regraft_transition_matrix
+  U.last_slots.resize(recs.size() * 3);
+  for (size_t k = 0; k < recs.size(); ++k)
+  {
+    U.last_slots[3 * k] = recs[k].m1; U.last_slots[3 * k + 1] = recs[k].m2; U.last_slots[3 * k + 2] = recs[k].m3;
+  }
+  U.classes = n_cls; U.last_count = count; U.last_keep = keep; U.valid = true;
+  if (I0->prof)
+  {
+    ++U.prof_n;
+    U.prof_cand += count;
+  }
+  // every stream has drained: clean at once -- the Lk(b) / dLk calls that follow can be served resident again
+  for (Instance *I : cls)
+  {
+    I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch;
+  }
+  return PHYHIP_SUCCESS;
+}
+
 } // namespace phyhip_host
 
 using namespace phyhip_host;
@@ -578,6 +990,146 @@ int phyhip_set_regraft_work_space(int instance, long long maxBytes)
     side_of(I).regraft.max_bytes = maxBytes ? (size_t)maxBytes : kRegraftWorkBytes;
     return 0;
   });
+}
+
+int phyhip_calculate_mixture_regraft_log_likelihoods(const int *instances, int count, const int *eigenIndices,
+                                                     const phyhip_regraft_candidate *candidates, int candidateCount, int keepCandidate,
+                                                     const double *classProba, const double *rMatWeight, const double *eFrqWeight,
+                                                     double rMatWeightSum, double eFrqWeightSum, double sumProbas, double *outLogLikelihoods,
+                                                     int *outWarnings)
+{
+  static const char *const who = "phyhip_calculate_mixture_regraft_log_likelihoods";
+  if (count < 1 || count > kMaxMixClasses) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: %d mixture classes (1..%d)", who, count, kMaxMixClasses);
+  if (!instances || !eigenIndices || !classProba || !rMatWeight || !eFrqWeight)
+    return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: a NULL per-class array", who);
+  if (candidateCount < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate count %d", who, candidateCount);
+  if (candidateCount > 0 && (!candidates || !outLogLikelihoods))
+    return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: a NULL array for %d candidates", who, candidateCount);
+  if (keepCandidate < -1 || keepCandidate >= candidateCount)
+    return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: keepCandidate %d of %d candidates", who, keepCandidate, candidateCount);
+  const MixRegraftCoef co{classProba, rMatWeight, eFrqWeight, rMatWeightSum, eFrqWeightSum, sumProbas};
+  Group *const G0 = get_group(instances[0]);
+  if (!G0)
+  {
+    for (int k = 1; k < count; ++k)
+      if (get_group(instances[k])) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d: sharded and plain class instances cannot be mixed", who, k);
+    if (candidateCount == 0)
+    { // nothing runs: the first instance is entered all the same
+      GET_INST(I, instances[0]);
+      (void)I;
+      return PHYHIP_SUCCESS;
+    }
+    std::vector<int> warn((size_t)candidateCount, 0);
+    if (const int rc = mixregraft_run(instances, count, eigenIndices, candidates, candidateCount, keepCandidate, co, outLogLikelihoods, warn.data()))
+      return rc;
+    if (outWarnings)
+      for (int k = 0; k < candidateCount; ++k) outWarnings[k] = warn[k];
+    return PHYHIP_SUCCESS;
+  }
+  // class instances that are one-process sharded instances of one shard layout: every shard scans its pattern range over its
+  // sub-instances; a candidate's shard sums are added here in shard order
+  std::vector<Group *> Gs;
+  int rc = mixture_groups(instances, count, Gs);
+  if (rc) return rc;
+  for (Group *G : Gs)
+    if ((rc = group_take_drain_error(G))) return rc;
+  if (candidateCount == 0) return PHYHIP_SUCCESS;
+  std::vector<double> part((size_t)candidateCount), sum((size_t)candidateCount, 0.0);
+  std::vector<int>    wpart((size_t)candidateCount), warn((size_t)candidateCount, 0);
+  for (size_t g = 0; g < G0->sub_id.size(); ++g)
+  {
+    int ids[kMaxMixClasses];
+    for (int k = 0; k < count; ++k) ids[k] = Gs[k]->sub_id[g];
+    if ((rc = mixregraft_run(ids, count, eigenIndices, candidates, candidateCount, keepCandidate, co, part.data(), wpart.data()))) return rc;
+    for (int k = 0; k < candidateCount; ++k)
+    {
+      sum[k] += part[k];
+      warn[k] |= wpart[k];
+    }
+  }
+  for (int k = 0; k < candidateCount; ++k) outLogLikelihoods[k] = sum[k];
+  if (outWarnings)
+    for (int k = 0; k < candidateCount; ++k) outWarnings[k] = warn[k];
+  return PHYHIP_SUCCESS;
+}
+
+int phyhip_get_mixture_regraft_partials(int firstInstance, int classIndex, double *outPartials, int *outScaleFactors)
+{
+  static const char *const who = "phyhip_get_mixture_regraft_partials";
+  return side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long lo, long long) {
+    auto &U = side_of(I).mixregraft;
+    if (!U.valid || !U.work.ptr)
+      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_calculate_mixture_regraft_log_likelihoods call with this first instance before it", who);
+    if (U.last_keep < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: the last call kept no candidate (keepCandidate -1)", who);
+    if (classIndex < 0 || classIndex >= U.classes) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d of %d", who, classIndex, U.classes);
+    const size_t  PS = (size_t)I->P * I->S;
+    const double *d_keep = (const double *)U.work.ptr;
+    const int    *d_exp = reinterpret_cast<const int *>(d_keep + (size_t)U.classes * PS) + (size_t)classIndex * mixregraft_exponent_ints(I);
+    if (outPartials) HIPCHK(hipMemcpy(outPartials + (size_t)lo * I->S, d_keep + (size_t)classIndex * PS, PS * sizeof(double), hipMemcpyDeviceToHost));
+    if (outScaleFactors) HIPCHK(hipMemcpy(outScaleFactors + lo, d_exp, (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+
+int phyhip_get_mixture_regraft_transition_matrix(int firstInstance, int classIndex, int candidate, int which, double *outMatrix)
+{
+  static const char *const who = "phyhip_get_mixture_regraft_transition_matrix";
+  if (which < 0 || which > 2) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: which %d (0..2)", who, which);
+  if (!outMatrix) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: outMatrix is NULL", who);
+  bool done = false; // (the matrices are the same on every shard: the first one answers)
+  return side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long, long long) {
+    if (done) return 0;
+    auto &U = side_of(I).mixregraft;
+    if (!U.valid || !U.work.ptr)
+      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_calculate_mixture_regraft_log_likelihoods call with this first instance before it", who);
+    if (classIndex < 0 || classIndex >= U.classes) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d of %d", who, classIndex, U.classes);
+    if (candidate < 0 || candidate >= U.last_count) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d of %d", who, candidate, U.last_count);
+    if (candidate < U.last_first)
+      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d's matrices have left the work space (the call ran in %d chunks, the last from candidate %d)",
+                  who, candidate, U.chunks, U.last_first);
+    const size_t  SS = (size_t)I->S * I->S;
+    const double *d_mats = (const double *)((const char *)U.work.ptr + mixregraft_keep_bytes(I, U.classes));
+    const size_t  slot = (size_t)U.last_slots[3 * (size_t)(candidate - U.last_first) + which];
+    HIPCHK(hipMemcpy(outMatrix, d_mats + (slot * U.classes + classIndex) * SS, SS * sizeof(double), hipMemcpyDeviceToHost));
+    done = true;
+    return 0;
+  });
+}
+
+int phyhip_set_mixture_regraft_work_space(int firstInstance, long long maxBytes)
+{
+  if (maxBytes < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_set_mixture_regraft_work_space: %lld bytes", maxBytes);
+  return side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long, long long) {
+    side_of(I).mixregraft.max_bytes = maxBytes ? (size_t)maxBytes : kRegraftWorkBytes;
+    return 0;
+  });
+}
+
+int phyhip_profile_read_mixture_regraft(int firstInstance, double *outKernelMs, int *outCalls, long long *outCandidates)
+{
+  double    ms = 0.0;
+  int       n = 0;
+  long long nc = 0;
+  bool      first = true; // (calls and candidates are the same on every shard; the time is added over the shards)
+  const int rc = side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long, long long) {
+    auto &U = side_of(I).mixregraft;
+    ms += U.prof_ms;
+    if (first)
+    {
+      n = U.prof_n;
+      nc = U.prof_cand;
+    }
+    first = false;
+    U.prof_ms = 0.0;
+    U.prof_n = 0;
+    U.prof_cand = 0;
+    return 0;
+  });
+  if (rc < 0) return rc;
+  if (outKernelMs) *outKernelMs = ms;
+  if (outCalls) *outCalls = n;
+  if (outCandidates) *outCandidates = nc;
+  return PHYHIP_SUCCESS;
 }
 
 int phyhip_profile_read_regraft(int instance, double *outKernelMs, int *outCalls, long long *outCandidates)

@@ -159,7 +159,7 @@ struct SideTimer
 
 // ---- what the units keep on the instance (Instance::side, made on first use) ------------------------------------------------------
 constexpr size_t kDistBandBytes = 128u << 20; // pairwise distances: the raw counts of one band of taxa stay below this by default
-constexpr size_t kRegraftWorkBytes = kDistBandBytes; // regraft scan: the work space stays below this by default (a longer list runs in chunks)
+constexpr size_t kRegraftWorkBytes = kDistBandBytes; // regraft scans (plain and mixture): the work space stays below this by default (a longer list runs in chunks)
 
 struct SideUnits
 {
@@ -213,6 +213,19 @@ struct SideUnits
     int       prof_n = 0;
     long long prof_cand = 0;                 // ... and the candidates they served
   } regraft;
+  struct
+  { // phyhip_calculate_mixture_regraft_log_likelihoods; all of it lives on the FIRST class instance (of each shard)
+    WorkSpace work;                          // kept vectors [class][P][S], their exponents, then one chunk's matrices, tile sums, sums, class table, records, lengths
+    size_t    max_bytes = kRegraftWorkBytes; // the bound on it (phyhip_set_mixture_regraft_work_space)
+    bool      valid = false;                 // a call has completed: the getters may read what it left
+    int       classes = 0;                   // of the last call: its classes, ...
+    int       chunks = 0, last_first = 0;    // ... its chunks, the first candidate of the last one
+    int       last_count = 0, last_keep = -1;
+    std::vector<int> last_slots;             // ... [candidate of the last chunk][3]: the matrix slots its record named
+    double    prof_ms = 0.0;                 // while profiling: its kernels (phyhip_profile_read_mixture_regraft)
+    int       prof_n = 0;
+    long long prof_cand = 0;                 // ... and the candidates they served
+  } mixregraft;
 };
 
 inline SideUnits &side_of(Instance *I)
@@ -224,7 +237,9 @@ inline SideUnits &side_of(Instance *I)
 inline void side_release(Instance *I) // phyhip_finalize_instance
 {
   if (!I->side) return;
-  for (WorkSpace *w : {&I->side->exact.out, &I->side->anc.work, &I->side->dist.work, &I->side->sup.slots, &I->side->sup.work, &I->side->regraft.work}) w->release();
+  for (WorkSpace *w : {&I->side->exact.out, &I->side->anc.work, &I->side->dist.work, &I->side->sup.slots, &I->side->sup.work, &I->side->regraft.work,
+                       &I->side->mixregraft.work})
+    w->release();
   if (I->side->brlen.h_out) (void)hipHostFree(I->side->brlen.h_out);
   delete I->side;
   I->side = nullptr;

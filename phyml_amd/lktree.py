@@ -455,3 +455,25 @@ class _InstanceView(capi.Instance):
 
     def close(self):
         self.id = None
+
+
+def Mixture_Regraft_Scan(trees, proba, r_mat_weight, e_frq_weight, r_sum, e_sum, sum_probas, b_sub, d_sub, link_is_left, l_sub, targets,
+                         l_left, l_rght):
+    """MIXT_Lk_Regraft_Scan: LkTree.Regraft_Scan over the class trees of a mixture (`trees`: one LkTree of one category per class, the
+    same topology and numbering) in one device call -- the log-likelihoods [n] MIXT_Lk would return for regrafting the subtree of edge
+    b_sub on node d_sub's side onto each edge of `targets`.  Edges and nodes are numbers of the first class tree; the lengths are the
+    mixture tree's (include/phyhip_lk.h)."""
+    t0, K, n = trees[0], len(trees), len(targets)
+    tr = (C.POINTER(t_tree_brlen) * K)(*[t.tree for t in trees])
+    da = lambda v: np.ascontiguousarray(v, dtype=np.float64)
+    pr, rw, ew = da(proba), da(r_mat_weight), da(e_frq_weight)
+    assert pr.size == K and rw.size == K and ew.size == K
+    tg = (C.POINTER(t_edge) * max(1, n))(*[t0.edge(int(b)) for b in targets])
+    ll, lr = da(l_left), da(l_rght)
+    assert ll.size == n and lr.size == n
+    out = np.zeros(n)
+    t0.L.MIXT_Lk_Regraft_Scan(tr, K, _dp(pr), _dp(rw), _dp(ew), C.c_double(r_sum), C.c_double(e_sum), C.c_double(sum_probas),
+                              t0.edge(int(b_sub)), t0.node(int(d_sub)), 1 if link_is_left else 0, C.c_double(l_sub), n, tg, _dp(ll), _dp(lr),
+                              _dp(out))
+    _raise_if_error()
+    return out
