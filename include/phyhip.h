@@ -761,6 +761,66 @@ int phyhip_set_mixture_regraft_work_space(int firstInstance, long long maxBytes)
    previous read; reading resets all three */
 int phyhip_profile_read_mixture_regraft(int firstInstance, double *outKernelMs, int *outCalls, long long *outCandidates);
 
+/* ---- three-edge length search (src/utilities.c:7120-7146: Triple_Dist) ------------------------------------------------------------- */
+
+/* Triple_Dist at K internal nodes in ONE call.  A candidate is a node a with its three OUTER vectors -- partials[i] is the vector
+   that looks AT the node along a->b[i] (a partials buffer, or a tip index < tipCount), which Triple_Dist never changes -- and the
+   three lengths a->b[i]->l->v.  Per candidate, one workgroup of one plain launch runs (phyml_amd/csrc/phyhip_triple.hip):
+     the matrices of the three lengths (PMat_Empirical as phyhip_update_transition_matrices builds them); then for i = 0, 1, 2
+       I_i      Update_Partial_Lk(tree, a->b[i], a): the join of the two other outer vectors through their current matrices in
+                ascending edge order -- (1,2), (0,2), (0,1) -- with its exponents, as the regraft scan computes it;
+       lkBegin  Br_Len_Opt's Lk(b[i]): Lk_Core through matrix i between I_i and partials[i].  PHYHIP_TRIPLE_NODE_IS_LEFT(i) says
+                that a is b[i]->left -- I_i is the LEFT operand; clear, partials[i] is, and must then be an internal buffer.
+                Summed in one fixed order: a thread's patterns in ascending order (pattern = thread + round * threads), the
+                wave's shuffle-down tree 32..1, the waves in wave order;
+       the eigen-basis products and per-pattern exponents of that edge (phyhip_update_eigen_lr's arithmetic), into the work space;
+       the search of phyhip_optimise_edge_length from (length[i], lkBegin): the same steps, the same per-pattern terms;
+       length[i] = best_l, matrix i rebuilt, and Br_Len_Opt's check lk_end < lk_begin - tol (src/optimiz.c:656): status 8.
+     A status of 3..8 is where the reference stops the program: the candidate stops there and its later searches report -1.
+     length[i] of the search that stopped is its best_l so far (what the host-driven search leaves in *l; matrix i is NOT rebuilt),
+     lnL / dLnL are that search's; the lengths of the edges not reached are the inputs.
+     keepCandidate (-1: none): I_1 and I_0 are rebuilt from the final lengths (:7141-7142) and kept with the final I_2 for
+     phyhip_get_triple_partials (host order [pattern][category][state], and the exponents [pattern]); entries of a pattern without
+     weight are 0.  Nothing is kept of a candidate that stopped.
+   The bits of a candidate's result depend on the candidate alone: not on K, its place in the list or the chunks a bounded work
+   space (phyhip_set_triple_work_space; 0: the default of 128 MiB; per candidate 3 C S S + P C S doubles and P ints, and the three
+   kept vectors once) cuts the call into.
+     A plain call: queued matrix work and partial updates run first, virtual buffers a candidate names are stored, the large-grid
+   resident workgroups leave, the call waits for the stream and leaves it clean.  Nothing of the instance changes but this work
+   space and the numerical warning (the last candidate's last evaluation's): not partials, exponents, the matrix table, site outputs
+   or dot_prod.
+     Not built (PHYHIP_ERROR_NO_IMPLEMENTATION, nothing launched; the caller runs Triple_Dist edge by edge): ranks of
+   phyhip_comm_init_rank, one-process sharded instances, PHYHIP_FLAG_CLASS_AXIS and PHYHIP_FLAG_GENERIC_LOOP instances, more than
+   one eigen system, states other than 4 / 20, more than 8 categories, more than 16 384 patterns.  A NaN length:
+   PHYHIP_ERROR_FLOATING_POINT.  iterMax outside 1 .. 1000, tol <= 0, an index out of range, a tip without its flag, count < 0,
+   keepCandidate outside -1 .. count - 1: PHYHIP_ERROR_OUT_OF_RANGE.  count == 0 succeeds. */
+#define PHYHIP_TRIPLE_NODE_IS_LEFT(i) (1 << (i))
+typedef struct
+{
+  int    partials[3];
+  int    flags;
+  double length[3];
+} phyhip_triple_candidate;
+typedef struct
+{
+  double length[3];                 /* on return */
+  double lnL, dLnL;                 /* tree->c_lnL / c_dlnL as Triple_Dist leaves them: the last search's that ran */
+  double lkBegin[3];                /* Br_Len_Opt's lk_begin of each search */
+  int    evaluations[3], status[3]; /* phyhip_optimise_edge_length's statuses; -1: not reached; 8: lk_end < lk_begin - tol */
+  int    warning;                   /* the last evaluation's */
+  int    reserved;
+} phyhip_triple_result;
+int phyhip_optimise_triples(int instance, const phyhip_triple_candidate *candidates, int count, int iterMax, double tol,
+                            int keepCandidate, phyhip_triple_result *outResults);
+/* I_which (0..2) of the kept candidate of the last call: outPartials [pattern][category][state], outScaleFactors [pattern]; either
+   may be NULL.  No call before it, no kept candidate, or one that stopped: PHYHIP_ERROR_OUT_OF_RANGE */
+int phyhip_get_triple_partials(int instance, int which, double *outPartials, int *outScaleFactors);
+/* bound on the work space in bytes (0: the default, 128 MiB); a longer list runs in chunks of at least one candidate */
+int phyhip_set_triple_work_space(int instance, long long maxBytes);
+/* while phyhip_profile(instance, 1): milliseconds of the kernel (HIP events on the instance's stream), the calls and the
+   evaluations their searches took since the previous read; reading resets all three */
+int phyhip_profile_read_triples(int instance, double *outKernelMs, int *outCalls, long long *outEvaluations);
+
 #ifdef __cplusplus
 }
 #endif

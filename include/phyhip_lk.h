@@ -121,7 +121,7 @@ typedef struct __Tree
   /* Br_Len_Opt (src/optimiz.c:607): appended, every offset above stays what it was */
   int      n_tot_bl_opt;      /* tree->n_tot_bl_opt: grows by one per step of Br_Len_Spline, as in the reference (the evaluations after
                                  the first, plus one where a bracket walk leaves [l_min, l_max] before its probe) */
-  int      bl_opt_evaluations, bl_opt_status; /* of the last Br_Len_Opt: dLk evaluations taken; phyhip_optimise_edge_length's status */
+  int      bl_opt_evaluations, bl_opt_status; /* of the last Br_Len_Opt: dLk evaluations taken; phyhip_optimise_edge_length's status, or 8: lk_end < lk_begin - tol */
   short    bl_opt_host_chain;  /* the route of Br_Len_Opt's search.  NO and YES: dLk() driven from the host, one round trip per probe -- the default,
                                  measured the faster route on all but one shape (profiles/brlen_opt.md); 2: the device call wherever it
                                  is built, the host-driven steps where it is not (the search is the same on both routes, probe by probe) */
@@ -184,6 +184,24 @@ void   Set_Update_Eigen_Lr(int yesno, t_tree *tree);
    stay with the caller. */
 phydbl Br_Len_Opt(phydbl *l, t_edge *b, t_tree *tree);
 phydbl Br_Len_Newton(phydbl *l, t_edge *b, t_tree *tree);
+/* Triple_Dist, src/utilities.c:7120-7146: the matrices of a->b[1] and a->b[2], then for each of the node's three edges
+   Update_Partial_Lk(tree, a->b[i], a) and Br_Len_Opt(&a->b[i]->l, a->b[i], tree), then the partials of b[1] and b[0] once more --
+   driven through the functions above, one round trip per call (the per-candidate route, and the one to take wherever
+   phyhip_optimise_triples refuses).  Changes the tree exactly as the reference does: the three lengths and matrices, the node's three
+   partial vectors, c_lnL, c_dlnL, n_tot_bl_opt.  Where a Br_Len_Opt fails (tree->bl_opt_status 3..8: the reference's program
+   ends there) and the exit handler returns, Triple_Dist returns at once: the later edges are not searched.  A tip: UNLIKELY. */
+phydbl Triple_Dist(t_node *a, t_tree *tree);
+/* What Triple_Dist would find at each of n internal nodes, in ONE device call (phyhip_optimise_triples): the three outer vectors of
+   a[k] and their flags are resolved as Update_Partial_Lk / Lk resolve them, the start lengths are the edges' own.  l_out[k]: the three
+   lengths Triple_Dist would leave on a[k]->b[0..2]; lnL[k]: its return value; status[k]: 0, or the status (3..8, include/phyhip.h)
+   of the search at which the reference would have stopped the program (the lengths of that node's later edges are then their
+   starts).  Any of the three may be NULL.  Updates queued before the call are seen.  The nodes are evaluated INDEPENDENTLY, each
+   from the tree as it stands: the tree's lengths, matrices, partial vectors, c_lnL and c_dlnL are left alone -- a caller that
+   accepts node k's result sets the lengths and runs the updates itself.  tree->n_tot_bl_opt grows by Br_Len_Opt's rule over every
+   search that ran.  Batching is the caller's, and so is the bail-out of Evaluate_List_Of_Regraft_Pos_Triple (src/spr.c:1139-1376)
+   at the first improving move: every node of the list is evaluated, the caller ignores the results behind that index.  Where
+   the device call is not built (include/phyhip.h) the exit handler runs; the caller then takes Triple_Dist node by node. */
+void Triple_Dist_Scan(t_tree *tree, int n, t_node **a, phydbl (*l_out)[3], phydbl *lnL, int *status);
 /* The regraft scan of one pruned subtree in ONE device call (phyhip_calculate_regraft_log_likelihoods): what Test_One_Spr_Target
    (src/spr.c:590-760) computes target by target -- the matrices of the two halves of the target edge and of b_arrow,
    Update_Partial_Lk(b_arrow, n_link), Lk(b_arrow) -- for n target edges at once.  The subtree is the vector of b_sub on d_sub's

@@ -33,6 +33,21 @@ class RegraftCandidate(C.Structure):
                 ("child1Length", C.c_double), ("child2Length", C.c_double), ("subtreeLength", C.c_double)]
 
 
+class TripleCandidate(C.Structure):
+    """phyhip_triple_candidate"""
+    _fields_ = [("partials", C.c_int * 3), ("flags", C.c_int), ("length", C.c_double * 3)]
+
+
+class TripleResult(C.Structure):
+    """phyhip_triple_result"""
+    _fields_ = [("length", C.c_double * 3), ("lnL", C.c_double), ("dLnL", C.c_double), ("lkBegin", C.c_double * 3),
+                ("evaluations", C.c_int * 3), ("status", C.c_int * 3), ("warning", C.c_int), ("reserved", C.c_int)]
+
+    def as_tuple(self):
+        """(lengths, lnL, dLnL, lkBegin, evaluations, statuses, warning): compares with == bit for bit (no NaN in a finished record)"""
+        return (tuple(self.length), self.lnL, self.dLnL, tuple(self.lkBegin), tuple(self.evaluations), tuple(self.status), self.warning)
+
+
 class InstanceDetails(C.Structure):
     _fields_ = [("resourceNumber", C.c_int), ("resourceName", C.c_char * 64), ("implName", C.c_char * 64),
                 ("flags", C.c_long), ("computeUnits", C.c_int), ("globalMemBytes", C.c_longlong)]
@@ -63,6 +78,7 @@ SYMBOLS = [
     "phyhip_set_regraft_work_space", "phyhip_profile_read_regraft",
     "phyhip_calculate_mixture_regraft_log_likelihoods", "phyhip_get_mixture_regraft_partials",
     "phyhip_get_mixture_regraft_transition_matrix", "phyhip_set_mixture_regraft_work_space", "phyhip_profile_read_mixture_regraft",
+    "phyhip_optimise_triples", "phyhip_get_triple_partials", "phyhip_set_triple_work_space", "phyhip_profile_read_triples",
 ]
 
 FLAG_SHARDED = 1 << 40  # PHYHIP_FLAG_SHARDED
@@ -106,6 +122,27 @@ BRENT_IT_MAX = 1000  # kBrentItMax of phyml_amd/csrc/phyhip_brlen.hip (src/utili
 BRLEN_MAX_PATTERNS = 16384  # kBrlenMaxPatterns: phyhip_optimise_edge_length refuses instances of more patterns (built and tested up to here; not where it is faster)
 BRLEN_THREADS = {4: 1024, 20: 512}  # kBrlenThreads<S>: the one workgroup of the search kernel
 BRLEN_KEEP = {4: 3, 20: 1}  # kBrlenKeep<S>: rounds of a lane whose inputs stay in registers across the probes
+
+TRIPLE_MAX_PATTERNS = 16384  # kTripleMaxPatterns: phyhip_optimise_triples refuses instances of more patterns
+TRIPLE_THREADS = {4: 512, 20: 256}  # kTripleThreads<S>: the workgroup of a candidate
+TRIPLE_KEEP = {4: 5, 20: 2}  # kTripleKeep<S>: rounds of a search lane whose inputs stay in registers across the probes
+TRIPLE_LK_END = 8  # the status of a search whose lk_end fell below lk_begin - tol (src/optimiz.c:656)
+
+
+def triple_node_is_left(i):
+    """PHYHIP_TRIPLE_NODE_IS_LEFT(i)"""
+    return 1 << i
+
+
+def triple_chunk_candidates(P, C, S, max_bytes=REGRAFT_WORK_BYTES):
+    """candidates per chunk of optimise_triples under a work-space bound, as include/phyhip.h states the layout: the three kept
+    vectors (P C S doubles and P ints rounded up to even each, the whole rounded up to 256 bytes), then per candidate 3 C S S + P C S
+    doubles, P ints rounded up to even and 136 bytes; at least one"""
+    pe = (P + 1) // 2 * 2
+    fixed = (3 * (P * C * S * 8 + pe * 4) + 255) // 256 * 256
+    per = (3 * C * S * S + P * C * S) * 8 + pe * 4 + 136
+    return max(1, (max_bytes - fixed) // per if max_bytes > fixed + per else 1)
+
 
 _lib = None
 
@@ -490,6 +527,34 @@ class Instance:
     def set_regraft_work_space(self, max_bytes):
         """phyhip_set_regraft_work_space: the bound on the scan's work space in bytes (0: the default)"""
         _chk(self.L.phyhip_set_regraft_work_space(self.id, C.c_longlong(int(max_bytes))))
+
+    # -- three-edge length search (src/utilities.c: Triple_Dist)
+    def optimise_triples(self, candidates, keep=-1, iter_max=BRENT_IT_MAX, tol=1e-3):
+        """phyhip_optimise_triples: candidates = iterable of ((outer vector 0, 1, 2), flags, (length 0, 1, 2)); keep: the candidate
+        whose three vectors stay for triple_partials().  Returns the list of TripleResult records."""
+        cand = list(candidates)
+        arr = (TripleCandidate * max(1, len(cand)))()
+        for k, (x, flags, ln) in enumerate(cand):
+            arr[k] = TripleCandidate((C.c_int * 3)(*[int(v) for v in x]), int(flags), (C.c_double * 3)(*[float(v) for v in ln]))
+        out = (TripleResult * max(1, len(cand)))()
+        _chk(self.L.phyhip_optimise_triples(self.id, arr, len(cand), int(iter_max), C.c_double(tol), int(keep), out))
+        return [out[k] for k in range(len(cand))]
+
+    def triple_partials(self, which):
+        """phyhip_get_triple_partials: (vector [P][C*S], scale exponents [P]) I_which of the kept candidate of the last call"""
+        v = np.zeros((self.P, self.C * self.S)); s = np.zeros(self.P, np.int32)
+        _chk(self.L.phyhip_get_triple_partials(self.id, int(which), _ptr(v), _ptr(s)))
+        return v, s
+
+    def set_triple_work_space(self, max_bytes):
+        """phyhip_set_triple_work_space: the bound on the call's work space in bytes (0: the default)"""
+        _chk(self.L.phyhip_set_triple_work_space(self.id, C.c_longlong(int(max_bytes))))
+
+    def profile_read_triples(self):
+        """(kernel ms, calls, evaluations) of the optimise_triples calls since the previous read, while profile(1)"""
+        ms = C.c_double(); n = C.c_int(); ev = C.c_longlong()
+        _chk(self.L.phyhip_profile_read_triples(self.id, C.byref(ms), C.byref(n), C.byref(ev)))
+        return ms.value, n.value, ev.value
 
     # -- regraft scan of a mixture: what the FIRST class instance keeps (mixture_regraft_log_likelihoods below)
     def mixture_regraft_partials(self, class_index):

@@ -777,9 +777,78 @@ phydbl Br_Len_Opt(phydbl *l, t_edge *b, t_tree *tree)
   { /* :656-661 */
     char msg[128];
     snprintf(msg, sizeof msg, "lk_beg = %f lk_end = %f", lk_begin, lk_end);
+    tree->bl_opt_status = 8; /* (phyhip_optimise_triples' word for this line; a caller behind a handler that returns can tell) */
     Lk_Exit("Br_Len_Opt", msg);
   }
   return tree->c_lnL;
+}
+
+/* ------------------------------------------------------------------------------------------------ */
+/* Triple_Dist (src/utilities.c:7120-7146)                                                              */
+/* ------------------------------------------------------------------------------------------------ */
+
+phydbl Triple_Dist(t_node *a, t_tree *tree)
+{
+  if (a->tax) return -1.e20; /* UNLIKELY, src/utilities.h:348 */
+  Update_PMat_At_Given_Edge(a->b[1], tree);
+  Update_PMat_At_Given_Edge(a->b[2], tree);
+
+  /* the reference's program ends inside a Br_Len_Opt that fails (statuses 3..8); behind an exit handler that returns, so does this */
+  for (int i = 0; i < 3; ++i)
+  {
+    Update_Partial_Lk(tree, a->b[i], a);
+    Br_Len_Opt(&a->b[i]->l, a->b[i], tree);
+    if (tree->bl_opt_status >= 3) return tree->c_lnL;
+  }
+
+  Update_Partial_Lk(tree, a->b[1], a);
+  Update_Partial_Lk(tree, a->b[0], a);
+  return tree->c_lnL;
+}
+
+/* Triple_Dist at n nodes in one device call; see include/phyhip_lk.h */
+void Triple_Dist_Scan(t_tree *tree, int n, t_node **a, phydbl (*l_out)[3], phydbl *lnL, int *status)
+{
+  if (n <= 0) return;
+  const t_mod *m = tree->mod;
+  phyhip_triple_candidate *c = (phyhip_triple_candidate *)calloc((size_t)n, sizeof *c);
+  phyhip_triple_result    *r = (phyhip_triple_result *)calloc((size_t)n, sizeof *r);
+  if (!c || !r) { free(c); free(r); Lk_Exit("Triple_Dist_Scan", "out of memory"); return; }
+  for (int k = 0; k < n; ++k)
+  {
+    if (a[k]->tax) { free(c); free(r); Lk_Exit("Triple_Dist_Scan", "node is not an internal node"); return; }
+    for (int i = 0; i < 3; ++i)
+    {
+      const t_edge *b = a[k]->b[i];
+      c[k].partials[i] = Child_Buffer(a[k], b); /* the vector Update_Partial_Lk(tree, b', a) reads across b */
+      if (a[k] == b->left) c[k].flags |= PHYHIP_TRIPLE_NODE_IS_LEFT(i);
+      c[k].length[i] = b->l;
+    }
+  }
+  const int rc = phyhip_optimise_triples(tree->b_inst, c, n, m->brent_it_max, m->min_diff_lk_local, -1, r);
+  if (rc < 0)
+  {
+    free(c); free(r);
+    Lk_Exit("phyhip_optimise_triples", phyhip_get_last_error());
+    return;
+  }
+  for (int k = 0; k < n; ++k)
+  {
+    for (int i = 0; i < 3; ++i)
+    {
+      if (l_out) l_out[k][i] = r[k].length[i];
+      const int ev = r[k].evaluations[i], st = r[k].status[i];
+      if (st >= 0 && ev > 0) tree->n_tot_bl_opt += ev - 1 + (st == 1 || st == 2 || st == 7 ? 1 : 0); /* Br_Len_Opt's rule */
+    }
+    if (lnL) lnL[k] = r[k].lnL;
+    if (status)
+    { /* the status (3..8) of the search at which the reference stops the program, else 0 */
+      status[k] = 0;
+      for (int i = 0; i < 3; ++i)
+        if (r[k].status[i] >= 3) { status[k] = r[k].status[i]; break; }
+    }
+  }
+  free(c); free(r);
 }
 
 /* Br_Len_Newton (a harness, not a reference function) keeps the call pattern of the caller Br_Len_Opt (src/optimiz.c:607-663): Lk(b) fills dot_prod, then the

@@ -16,8 +16,10 @@
 //   phyhip_pars.hip      parsimony scores, Update_Partial_Pars / Pars (Fitch and step-matrix kernels, a queue and entry points of its own)
 //   phyhip_brlen.hip     one edge's branch-length search, Br_Len_Opt / Br_Len_Spline (one one-workgroup kernel, entry points of its own)
 //   phyhip_regraft.hip   the regraft scan of an SPR move: K candidates {two children, subtree, three lengths} in one call (matrix, scan
-//                        and sum kernels, entry points of its own)
-//   phyhip_side.hpp      the host layer those last seven share (host code only): the work space grown on use, the walk over the plain
+//                        and sum kernels, entry points of its own); its device functions: phyhip_regraft_dev.hpp
+//   phyhip_triple.hip    Triple_Dist at K nodes in one call: per candidate one workgroup runs three joins, products and edge-length
+//                        searches in sequence (one kernel, entry points of its own)
+//   phyhip_side.hpp      the host layer those last eight share (host code only): the work space grown on use, the walk over the plain
 //                        instance or every shard, the refusals by kind of instance, the kernel timer, Instance::side
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --

@@ -1,5 +1,5 @@
 // phyhip_side.hpp -- the host layer of the units beside the hot path (phyhip_exact.hip, phyhip_ancestral.hip, phyhip_dist.hip,
-// phyhip_support.hip, phyhip_pars.hip, phyhip_brlen.hip, phyhip_regraft.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
+// phyhip_support.hip, phyhip_pars.hip, phyhip_brlen.hip, phyhip_regraft.hip, phyhip_triple.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
 // by kind of instance, the kernel timer of a profiled instance, and what those units keep on the instance.  Host code only.
 #pragma once
 #include "phyhip_host.hpp"
@@ -226,6 +226,15 @@ struct SideUnits
     int       prof_n = 0;
     long long prof_cand = 0;                 // ... and the candidates they served
   } mixregraft;
+  struct
+  { // phyhip_optimise_triples
+    WorkSpace work;                          // the three kept vectors, their exponents, then one chunk's matrices, products, exponents, records, results
+    size_t    max_bytes = kRegraftWorkBytes; // the bound on it (phyhip_set_triple_work_space)
+    bool      keep_valid = false;            // the last call kept a candidate that ran to its end: phyhip_get_triple_partials may read it
+    double    prof_ms = 0.0;                 // while profiling: its kernel (phyhip_profile_read_triples)
+    int       prof_n = 0;
+    long long prof_evals = 0;                // ... and the evaluations its searches took
+  } triple;
 };
 
 inline SideUnits &side_of(Instance *I)
@@ -238,7 +247,7 @@ inline void side_release(Instance *I) // phyhip_finalize_instance
 {
   if (!I->side) return;
   for (WorkSpace *w : {&I->side->exact.out, &I->side->anc.work, &I->side->dist.work, &I->side->sup.slots, &I->side->sup.work, &I->side->regraft.work,
-                       &I->side->mixregraft.work})
+                       &I->side->mixregraft.work, &I->side->triple.work})
     w->release();
   if (I->side->brlen.h_out) (void)hipHostFree(I->side->brlen.h_out);
   delete I->side;

@@ -91,7 +91,7 @@ def load():
         L = C.CDLL(LK_LIB_PATH)
         L.Make_Tree_From_Edges.restype = C.POINTER(t_tree_brlen)
         L.Make_Model_Basic.restype = C.POINTER(t_mod)
-        for f in ("Lk", "dLk", "Br_Len_Newton", "Br_Len_Opt", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk", "Statistics_To_SH", "Statistics_to_RELL"):
+        for f in ("Lk", "dLk", "Br_Len_Newton", "Br_Len_Opt", "Triple_Dist", "Update_Lk_At_Given_Edge", "Get_Exact_Site_Lk", "Statistics_To_SH", "Statistics_to_RELL"):
             getattr(L, f).restype = C.c_double
         # tests must survive the reference's print-and-Exit() convention
         L.Set_Exit_Handler(_exit_handler)
@@ -393,6 +393,29 @@ class LkTree:
                                n, tg, _dp(ll), _dp(lr), _dp(out))
         _raise_if_error()
         return out
+
+    def Triple_Dist(self, a, force_host_chain=True, force_device=False):
+        """Triple_Dist(a, tree) (src/utilities.c:7120) at node number a, driven call by call through this layer's Update_Partial_Lk and
+        Br_Len_Opt (whose search takes the route the two flags name, as LkTree.Br_Len_Opt's do); changes the tree as the reference
+        does.  Returns ((l0, l1, l2), c_lnL, growth of n_tot_bl_opt)."""
+        tr = self.tree.contents
+        tr.bl_opt_host_chain = 2 if force_device else (1 if force_host_chain else 0)
+        before = tr.n_tot_bl_opt
+        v = self.L.Triple_Dist(self.node(int(a)), self.tree)
+        tr.bl_opt_host_chain = 0
+        _raise_if_error()
+        nd = self.node(int(a)).contents
+        return tuple(nd.b[i].contents.l for i in range(3)), v, tr.n_tot_bl_opt - before
+
+    def Triple_Dist_Scan(self, nodes):
+        """Triple_Dist_Scan: what Triple_Dist would find at each node of `nodes`, each from the tree as it stands, in one device call;
+        the tree's lengths, buffers and c_lnL are left alone (include/phyhip_lk.h).  Returns (lengths [n][3], lnL [n], status [n])."""
+        n = len(nodes)
+        nd = (C.POINTER(t_node) * max(1, n))(*[self.node(int(a)) for a in nodes])
+        l_out = np.zeros((n, 3)); lnl = np.zeros(n); st = np.zeros(n, np.int32)
+        self.L.Triple_Dist_Scan(self.tree, n, nd, _dp(l_out), _dp(lnl), st.ctypes.data_as(C.c_void_p))
+        _raise_if_error()
+        return l_out, lnl, st
 
     @property
     def s_opt(self):
