@@ -24,7 +24,15 @@ DBL_MIN = sys.float_info.min
 BRENT_IT_MAX = 1000
 SPLINE, LOWER, UPPER, NO_ROOT, BRACKET, TOO_LONG, NAN, CAP = range(8)
 
-Result = namedtuple("Result", "l lnL dlnL evaluations status n_tot best_from decisions spline probes")
+Result = namedtuple("Result", "l lnL dlnL evaluations status n_tot best_from decisions spline probes roots")
+
+
+def ieee_div(x, y):
+    """x / y as C's double division gives it: x / 0 = +-inf, 0 / 0 = nan (Python raises ZeroDivisionError there)"""
+    try:
+        return x / y
+    except ZeroDivisionError:
+        return float("nan") if x == 0.0 or x != x else math.copysign(float("inf"), x) * math.copysign(1.0, y)
 
 
 def trip_cap(frm, l_max):
@@ -44,19 +52,14 @@ def spline_roots(u, v, fu, fv, dfu, dfv):
     C_ = fv - fu + a_
     disc = B_ * B_ - 4. * A_ * C_
     D_ = math.sqrt(disc) if disc >= 0.0 else float("nan")
-
-    def div(x, y):
-        try:
-            return x / y
-        except ZeroDivisionError:
-            return float("nan") if x == 0.0 or x != x else math.copysign(float("inf"), x) * math.copysign(1.0, y)
-    r1 = div(-B_ - D_, 2. * A_)
-    r2 = div(-B_ + D_, 2. * A_)
+    r1 = ieee_div(-B_ - D_, 2. * A_)
+    r2 = ieee_div(-B_ + D_, 2. * A_)
     return r1 * (v - u) + u, r2 * (v - u) + u
 
 
 def pick_root(u, v, root1, root2):
-    """:2358-2376: (which, new_l or None) -- which: 1 / 2 the accepted root, 0 none but u / v within [0.9, 1.1], -1 the assert"""
+    """:2358-2376: (which, new_l or None) -- which: 1 / 2 the accepted root, 0 none but u / v within [0.9, 1.1], -1 the assert.
+    u / v is the C division of :2372: u / 0 is +-inf (the assert), 0 / 0 is nan (neither comparison holds: no assert)"""
     ok1 = root1 > u and root1 < v
     ok2 = root2 > u and root2 < v
     if abs(root1 - u) < 1.E-5: ok1 = True
@@ -69,7 +72,7 @@ def pick_root(u, v, root1, root2):
         return 1, root1
     if ok2:
         return 2, root2
-    q = u / v if v != 0.0 else float("nan")
+    q = ieee_div(u, v)
     if q > 1.1 or q < 0.9:
         return -1, None
     return 0, None
@@ -100,12 +103,13 @@ def root_spread(sp, b_lnl, b_dlnl):
     return worst
 
 
-def br_len_spline(dlk, l0, init_lnL, l_min, l_max, n_iter_max=BRENT_IT_MAX, tol=1.E-3):
+def br_len_spline(dlk, l0, init_lnL, l_min, l_max, n_iter_max=BRENT_IT_MAX, tol=1.E-3, cap=None):
     """Returns Result: l = best_l, lnL = best_lnL, dlnL = c_dlnL as the search leaves it, the dLk evaluations, the status word of
     phyhip_optimise_edge_length, n_tot (the growth of tree->n_tot_bl_opt), best_from ("start": best_l is the start itself,
     "geometric": a length of one of the two walks, "spline": the spline's root), the decisions [(kind, margin)], the spline step
-    (u, v, fu, fv, dfu, dfv, which root, root) or None, and the probes [(l, lnL, dlnL)]."""
-    dec, probes = [], []
+    (u, v, fu, fv, dfu, dfv, which root, root) or None, the probes [(l, lnL, dlnL)], and per turn of the spline loop
+    (u, v, root1, root2, which).  cap: the trips either walk may take (None: trip_cap(l_min, l_max), the device call's bound)."""
+    dec, probes, roots = [], [], []
     state = dict(n=0, n_tot=0)
 
     def ev(l):
@@ -115,7 +119,7 @@ def br_len_spline(dlk, l0, init_lnL, l_min, l_max, n_iter_max=BRENT_IT_MAX, tol=
         return lc, lnl, dl
 
     def out(l, lnl, dl, status, best_from, spline=None):
-        return Result(l, lnl, dl, state["n"], status, state["n_tot"], best_from, dec, spline, probes)
+        return Result(l, lnl, dl, state["n"], status, state["n_tot"], best_from, dec, spline, probes, roots)
 
     if l0 != l0:
         return out(l0, init_lnL, 0.0, NAN, "start")
@@ -123,7 +127,7 @@ def br_len_spline(dlk, l0, init_lnL, l_min, l_max, n_iter_max=BRENT_IT_MAX, tol=
     init_l = best_l = l0
     best_lnL = old_lnL = init_lnL
     best_from = "start"
-    cap_lower = cap_upper = trip_cap(l_min, l_max)
+    cap_lower = cap_upper = trip_cap(l_min, l_max) if cap is None else cap
     new_l = -1.
 
     l, c_lnL, c_dlnL = ev(l0)
@@ -173,6 +177,7 @@ def br_len_spline(dlk, l0, init_lnL, l_min, l_max, n_iter_max=BRENT_IT_MAX, tol=
     while True:
         root1, root2 = spline_roots(u, v, fu, fv, dfu, dfv)
         which, r = pick_root(u, v, root1, root2)
+        roots.append((u, v, root1, root2, which))
         dec.append(("root", root_margin(u, v, root1, root2)))
         if which < 0:
             return out(best_l, best_lnL, c_dlnL, NO_ROOT, best_from, spline)

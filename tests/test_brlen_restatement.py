@@ -9,7 +9,12 @@ differs at 113 of the 1 685 records, by at most 3.3e-16 relative): measured larg
 lk_begin 3.26e-16, c_lnL 1.08e-15, the spline's l_out 6.94e-12, and c_dlnL 1.765e-07: the spline's root inherits the last bits of
 four sums, and c_dlnL is the derivative AT that root -- a sum of terms of both signs that nearly cancels at the optimum, so the
 root's 7e-12 shows as 5.4e-09 absolute in it (profiles/brlen_opt.md).  Each quantity is held at eight times ITS OWN largest
-difference.  Thin decisions were removed when the fixtures were made; no record is skipped here."""
+difference.  Thin decisions were removed when the fixtures were made; no record is skipped here.
+
+One correction since: brlen_ref.pick_root now divides as C does at src/optimiz.c:2372 (`u / 0` = +-inf, the assert; `0 / 0` = NaN,
+no assert) where it answered NaN for every v == 0.  No record here has v == 0 -- every number above is unchanged -- which is why
+these fixtures could not see it; tests/test_brlen_step_restatement.py, which holds phyhip_brlen_step.h to the restatement on
+synthetic functions, did (the header was right), and keeps the case."""
 import os
 
 import numpy as np

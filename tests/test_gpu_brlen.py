@@ -215,15 +215,31 @@ def test_geometry(ns, c, p):
 
 
 # ---- the tail's branches inside the loop ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,edges", [("nucleic_zero_w", (0, 11, 52)), ("synth_nt_300x40", (3, 150, 400))])
+@pytest.mark.parametrize("name,edges", [("nucleic_zero_w", (0, 11, 52)), ("synth_nt_300x40", (3, 150, 400)), ("synth_aa_90x24", (3, 88, 170))])
 def test_zero_weights_and_scale_exponents(name, edges):
-    """bootstrap-like zero-weight patterns, and a deep tree whose edge evaluations carry nonzero scale exponents"""
+    """bootstrap-like zero-weight patterns, and a deep tree whose edge evaluations carry nonzero scale exponents (at 20 states on
+    every one of the chosen edges: the probes read them from the edge's `fact`)"""
     d = _golden(name)
     t, ot = device_tree_from_golden(d)
     try:
         _check_synthetic(t, ot, edges, (1.0, 0.05, 20.0), name)
         if name == "synth_nt_300x40":
             assert np.any(ot.fact_sum_scale != 0)
+        if name == "synth_aa_90x24":
+            for e in edges:
+                ot.lk(e)
+                assert np.any(ot.fact_sum_scale != 0), e
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("ns", [4, 20])
+def test_the_documented_maximum_of_patterns(ns):
+    """capi.BRLEN_MAX_PATTERNS patterns, 8 categories: one search at scale 1.0 on both routes"""
+    assert capi.BRLEN_MAX_PATTERNS == 16384
+    t, ot, tree, st = synthetic_pair(6, 16384, ns, 8, seed=3)
+    try:
+        _check_synthetic(t, ot, (2,), (1.0,), ("maximum", ns))
     finally:
         t.close()
 

@@ -71,6 +71,8 @@ class Mixture:
         n = SMALL_SHAPES[ns][0] if n is None else n
         P = SMALL_SHAPES[ns][1] if P is None else P
         ot0, tree, st, tv, wg = synthetic_oracle(n, P, ns, 1, seed, lmin, lmax, wght, 1, 5)
+        pick = [k % len(models) for k in range(K)]     # more classes than the fixture has: its classes over again
+        models, factors = [models[k] for k in pick], [factors[k] for k in pick]
         M = cls(models[:K], factors[:K], sums, n, tree.edge_left, tree.edge_rght, tree.edge_len, wg, ot0.tip_vec, ot0.tip_ds, ot0.tip_amb, **kw)
         M.tree = tree
         return M
@@ -162,7 +164,8 @@ def small():
 
 # 1. small shapes ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ns,P,K", [(4, 300, 1), (4, 300, 2), (4, 300, 4), (4, 1, 4), (4, 255, 4), (4, 256, 4), (4, 257, 4),
-                                    (20, 270, 1), (20, 270, 2), (20, 270, 4)])
+                                    (20, 270, 1), (20, 270, 2), (20, 270, 4),
+                                    (4, 300, 3), (4, 300, 5), (20, 270, 3), (20, 270, 5)])   # class counts that are no power of two
 def test_small_shapes(ns, P, K):
     M = Mixture.synthetic(ns, P, K)
     try:

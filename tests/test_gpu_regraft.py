@@ -170,7 +170,9 @@ def small():
 
 # 1. small shapes ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ns,P,Cc", [(4, 300, 1), (4, 300, 4), (4, 300, 8), (4, 1, 4), (4, 255, 4), (4, 256, 4), (4, 257, 4),
-                                     (20, 270, 1), (20, 270, 4), (20, 270, 8)])
+                                     (20, 270, 1), (20, 270, 4), (20, 270, 8),
+                                     # category counts that are no power of two (4 states: the unrolled `if (c < q.C)` of the registers)
+                                     (4, 300, 3), (4, 300, 5), (4, 300, 7), (20, 270, 3), (20, 270, 5), (20, 270, 7)])
 def test_small_shapes(ns, P, Cc):
     t, ot, tree = prepared(SMALL_SHAPES[ns][0], P, ns, Cc)
     try:
@@ -204,10 +206,13 @@ def test_small_shapes(ns, P, Cc):
 
 
 # 2. rare branches: each asserted on the oracle's own output first ---------------------------------------------------------------------
-def test_scaling_exponents_zero_inherited_and_own():
+@pytest.mark.parametrize("ns", [4, 20])
+def test_scaling_exponents_zero_inherited_and_own(ns):
     """A deep tree with long branches: among the kept exponent vectors are 0, sums inherited from the children, and a candidate's own
-    +256 on top of what it inherited or on nothing."""
-    t, ot, tree, st = synthetic_pair(300, 24, 4, 4, seed=5, lmin=1.0, lmax=4.0)
+    +256 on top of what it inherited or on nothing.  (20 states: the join is recomputed in a second pass that applies 2^256 and reads
+    the inherited exponents through the fragment-major layout -- other code than the 4-state registers.)"""
+    t, ot, tree, st = (synthetic_pair(300, 24, 4, 4, seed=5, lmin=1.0, lmax=4.0) if ns == 4 else
+                       synthetic_pair(120, 24, 20, 4, seed=5, lmin=1.0, lmax=3.0))
     try:
         t.Set_Both_Sides(True)
         t.Lk(None)
@@ -219,6 +224,7 @@ def test_scaling_exponents_zero_inherited_and_own():
         zero = [i for i in order if total[i] == 0]
         scaled = [i for i in order if total[i] > 0]
         assert zero and scaled
+        assert {int(v) for p, sc in chk.buf.values() for v in np.unique(sc[w])} == {0, 256, 512}
         rng = np.random.default_rng(2)
         pairs = [(zero[0], zero[1]), (scaled[0], zero[0]), (scaled[-1], scaled[-2])]
         pairs += [(int(rng.choice(order)), int(rng.choice(order))) for _ in range(40)]
@@ -325,6 +331,49 @@ def test_without_lk_scaling():
         assert all(not np.any(r[3]) for r in refs)                                 # no exponent anywhere
         assert any(0.0 < r[2][r[2] > 0].min() < 2.0 ** -256 for r in refs)         # ... where scaling would have stepped in
         check_scan(t, chk, cands, [0, 3, 7], "apply_lk_scaling = 0", two_call=False)
+    finally:
+        t.close()
+
+
+def test_without_lk_scaling_at_twenty_states():
+    """the same at 20 states: the second pass of the join must not apply 2^256 and the tail's f stays 0 (the smallest positive
+    partial of the tree is 2.0e-206, far below 2^-256)"""
+    t, ot, tree, st = synthetic_pair(120, 24, 20, 4, seed=5, lmin=1.0, lmax=3.0, apply_scaling=0)
+    try:
+        t.Set_Both_Sides(True)
+        t.Lk(None)
+        ot.lk(None, both_sides=True)
+        assert ot.apply_scaling == 0 and not any(np.any(s) for s in ot.scale.values())
+        assert min(float(p[p > 0].min()) for p in ot.plk.values()) < 1e-200
+        chk = Checker.of_tree(t, ot)
+        cands = raw_records(t, ot, 8, seed=4)
+        refs = [chk.candidate(c) for c in cands]
+        assert all(not np.any(r[3]) for r in refs)
+        assert any(0.0 < r[2][r[2] > 0].min() < 2.0 ** -256 for r in refs)
+        check_scan(t, chk, cands, [0, 3, 7], "apply_lk_scaling = 0, 20 states", two_call=False)
+    finally:
+        t.close()
+
+
+def test_invariant_sites_at_twenty_states_with_scaled_constant_patterns():
+    """+I at 20 states on a deep tree with planted constant columns: in most candidates some constant pattern reaches the tail with a
+    nonzero exponent (the kept vector's plus the subtree's; asserted on the oracle), in some none does"""
+    t, ot, tree, st = synthetic_pair(90, 24, 20, 4, seed=5, lmin=4.0, lmax=8.0, pinvar=0.2, constant_every=4)
+    try:
+        t.Set_Both_Sides(True)
+        t.Lk(None)
+        ot.lk(None, both_sides=True)
+        const = ot.invar >= 0
+        assert ot.m.invar_model == 1 and ot.m.pinvar == 0.2 and 4 <= int(const.sum()) < ot.P
+        chk = Checker.of_tree(t, ot)
+        cands = raw_records(t, ot, 16, seed=9)
+        scaled = []
+        for c in cands:
+            f = chk.candidate(c)[3] + (chk.buf[c[2]][1] if c[2] >= ot.n else 0)
+            scaled.append(bool(np.any(f[const] != 0)))
+        assert sum(scaled) >= 4 and not all(scaled), scaled
+        check_scan(t, chk, cands, [-1, 0, 7, 15], "+I at 20 states", two_call=False)
+        check_scan(t, chk, cands[:3], [0], "+I at 20 states")
     finally:
         t.close()
 

@@ -61,9 +61,21 @@ def _bounds(ot, r):
     return b_lnl, b_dlnl
 
 
-def _staged(ot, a, cand, res, what, iter_max=brlen_ref.BRENT_IT_MAX):
+def _tied_lengths(r, l_start, lk_begin, b_lnl):
+    """Where a walk crosses a stretch on which lnL moves by less than the sums' own bound (saturated trees: the slow category has
+    clamped at l_min and the others carry no slope), `c_lnL > best_lnL` is decided by the order of the sum.  Both sides evaluate the
+    same lengths; each device lnL lies within B_lnl of the oracle's, so the length the device calls best has an oracle lnL within
+    2 B_lnl of the oracle's best.  Returns those lengths -- empty unless the replay itself took a best-so-far decision inside
+    B_lnl (a record without one is held to the bits)."""
+    if not any(k == "best" and m <= b_lnl for k, m in r.decisions):
+        return set()
+    tied = {p[0] for p in r.probes[1:] if abs(p[1] - r.lnL) <= 2.0 * b_lnl}      # (the first probe's lnL is never compared)
+    return tied | ({l_start} if abs(lk_begin - r.lnL) <= 2.0 * b_lnl else set())
+
+
+def _staged(ot, a, cand, res, what, iter_max=brlen_ref.BRENT_IT_MAX, ties=False):
     """the device's record of one candidate against the CPU replay of each search from the lengths the device held in front of it;
-    the oracle tree is put back as it was"""
+    the oracle tree is put back as it was.  ties: see _tied_lengths (the deep saturated trees only)."""
     e = triple_ref.edges_of(ot, a)
     l0 = [float(ot.len[x]) for x in e]
     held = list(cand[2])
@@ -82,13 +94,16 @@ def _staged(ot, a, cand, res, what, iter_max=brlen_ref.BRENT_IT_MAX):
             b_lnl, b_dlnl = _bounds(ot, r)
             assert (res.evaluations[i], res.status[i]) == (r.evaluations, s.status), (what, a, i, tuple(res.evaluations), tuple(res.status), r.evaluations, s.status)
             assert abs(res.lkBegin[i] - s.lk_begin) <= b_lnl, (what, a, i, res.lkBegin[i], s.lk_begin, b_lnl)
-            if r.best_from != "spline":
+            tied = _tied_lengths(r, held[i], s.lk_begin, b_lnl) if ties and r.best_from != "spline" and res.length[i] != r.l else set()
+            if tied:
+                assert res.length[i] in tied, (what, a, i, res.length[i].hex(), r.l.hex(), sorted(tied))
+            elif r.best_from != "spline":
                 assert res.length[i] == r.l, (what, a, i, res.length[i].hex(), r.l.hex())
             else:
                 spread = brlen_ref.root_spread(r.spline, b_lnl, b_dlnl)
                 assert abs(res.length[i] - r.l) <= 8.0 * spread, (what, a, i, res.length[i], r.l, spread)
             if i == 2 or res.status[i + 1] < 0:   # c_lnL as Triple_Dist leaves it: the last search's best_lnL (the oracle still holds its products)
-                if r.best_from == "start":
+                if r.best_from == "start" and res.length[i] == r.l:
                     assert res.lnL == res.lkBegin[i], (what, a, i)
                 else:
                     assert abs(res.lnL - ot.dlk(res.length[i])[1]) <= b_lnl, (what, a, i, res.lnL, ot.dlk(res.length[i])[1], b_lnl)
@@ -253,17 +268,26 @@ def _geometry():
             for p in sorted({1, w // cp - 1, w // cp, w // cp + 1, r * w // cp + 1} | ({w - 1, w, w + 1} if c == 1 else set())):
                 if p >= 1:
                     out.append((ns, c, p))
+        # category counts that are no power of two: CP > C, triple_fetch's padded lanes c0 >= C read category 0 and dlk_lane masks them
+        for c in (3, 5, 7):
+            cp = 1 << (c - 1).bit_length()
+            out.extend((ns, c, p) for p in sorted({1, w // cp, w // cp + 1}))
     return out
 
 
-def _check_synthetic(t, ot, nodes, what, scales=SCALES, keep_at=0):
+def _check_synthetic(t, ot, nodes, what, scales=SCALES, keep_at=0, ties=False):
+    """returns the records [(scale, node, TripleResult.as_tuple())] and the exponents of the kept vectors per scale"""
     _prepare(t, ot)
+    records, kept_exponents = [], []
     for scale in scales:
         cands = [_candidate(t, a, scale) for a in nodes]
         res = t.inst.optimise_triples(cands, keep=keep_at)
         for a, c, r in zip(nodes, cands, res):
-            _staged(ot, a, c, r, (what, scale))
+            _staged(ot, a, c, r, (what, scale), ties=ties)
+            records.append((scale, a, r.as_tuple()))
         _kept_vectors(t, ot, nodes[keep_at], res[keep_at], (what, scale))
+        kept_exponents.append([t.inst.triple_partials(i)[1] for i in range(3)])
+    return records, kept_exponents
 
 
 @pytest.mark.parametrize("ns,c,p", _geometry())
@@ -312,23 +336,34 @@ def test_each_operand_as_a_tip_and_both_values_of_each_flag():
             t.close()
 
 
+def _own_and_inherited(ot, a):
+    """whether some vector towards node a adds an exponent of its own, and whether some inherits one from its children"""
+    own = inherited = False
+    for e in triple_ref.edges_of(ot, a):
+        side = 0 if a == ot.el[e] else 1
+        kids = [ot.scale[k] for k in ot.op_for(e, a)[1] if k in ot.scale]
+        below = sum(kids) if kids else 0
+        inherited |= bool(np.any(below != 0))
+        own |= bool(np.any(ot.scale[(e, side)] != below))
+    return own, inherited
+
+
 @pytest.mark.parametrize("name,nodes", [("nucleic_zero_w", (54, 60, 77, 105)), ("synth_nt_300x40", (300, 371, 450, 597)),
-                                        ("nucleic_gtr_g4_inv", (54, 71, 105))])
+                                        ("nucleic_gtr_g4_inv", (54, 71, 105)), ("synth_aa_90x24", (90, 97, 98))])
 def test_zero_weights_scale_exponents_and_invariant_sites(name, nodes):
-    """bootstrap-like zero-weight patterns; a deep tree whose vectors carry inherited exponents and whose joins add their own; +I"""
+    """bootstrap-like zero-weight patterns; a deep tree whose vectors carry inherited exponents and whose joins add their own, at
+    both state counts (20 states: the join's second pass applies 2^256 -- other code than the 4-state registers); +I"""
     d = _golden(name)
     t, ot = device_tree_from_golden(d)
     try:
         _check_synthetic(t, ot, nodes, name, keep_at=1)
-        if name == "synth_nt_300x40":
+        if name in ("synth_nt_300x40", "synth_aa_90x24"):
             own = inherited = False
             for a in nodes:
-                for e in triple_ref.edges_of(ot, a):
-                    side = 0 if a == ot.el[e] else 1
-                    kids = [ot.scale[k] for k in ot.op_for(e, a)[1] if k in ot.scale]
-                    below = sum(kids) if kids else 0
-                    inherited |= bool(np.any(below != 0))
-                    own |= bool(np.any(ot.scale[(e, side)] != below))
+                own_a, inherited_a = _own_and_inherited(ot, a)
+                own, inherited = own or own_a, inherited or inherited_a
+                if name == "synth_aa_90x24":
+                    assert own_a and inherited_a, a      # at 20 states every one of the three nodes has both
             assert own and inherited
         if name == "nucleic_zero_w":
             assert np.any(ot.wght == 0)
@@ -371,6 +406,227 @@ def test_near_zero_and_l_max_starts_and_iter_max():
             t.s_opt.brent_it_max = capi.BRENT_IT_MAX
         assert t.tree.contents.bl_opt_status == 5 and t.n_tot_bl_opt - before == r.evaluations[0] - 1
         assert [t.edge(b).contents.l for b in e[1:]] == list(lens[1:])
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("ns,P", [(4, 40), (20, 24)])
+def test_without_lk_scaling(ns, P):
+    """apply_lk_scaling = 0 on a deep tree with long branches: partials far below 2^-256 and no exponent anywhere -- not in the oracle's
+    vectors, not among the kept ones, f = 0 in the tail; every 13th internal node at the three scalings"""
+    t, ot, tree, st = synthetic_pair(120, P, ns, 4, seed=5, lmin=1.0, lmax=3.0, apply_scaling=0)
+    try:
+        nodes = list(range(ot.n, 2 * ot.n - 2))[::13]
+        records, kept_exponents = _check_synthetic(t, ot, nodes, ("apply_lk_scaling = 0", ns), keep_at=3, ties=True)
+        assert ot.apply_scaling == 0 and not any(np.any(s) for s in ot.scale.values())
+        assert min(float(p[p > 0].min()) for p in ot.plk.values()) < 2.0 ** -256      # ... where scaling would have stepped in
+        assert len(records) == 3 * len(nodes) and len(nodes) == 10
+        for scale, a, (length, lnl, dlnl, lkb, evals, status, warning) in records:
+            assert all(s in (0, 1, 2) for s in status) and warning == 0 and np.isfinite(lnl), (ns, scale, a, status, warning, lnl)
+        assert not any(np.any(s) for per_scale in kept_exponents for s in per_scale)
+        assert t.inst.numerical_warning() == 0
+    finally:
+        t.close()
+
+
+def test_invariant_sites_at_twenty_states_with_scaled_constant_patterns():
+    """+I at 20 states on a deep tree: planted constant columns, and branches long enough that constant patterns carry a nonzero
+    exponent on every edge of the chosen nodes (asserted on the oracle) -- Invariant_Lk's scaled branch inside the probes"""
+    t, ot, tree, st = synthetic_pair(90, 24, 20, 4, seed=5, lmin=4.0, lmax=8.0, pinvar=0.2, constant_every=4)
+    try:
+        nodes = (95, 97, 98)
+        _prepare(t, ot)
+        const = ot.invar >= 0
+        assert ot.m.invar_model == 1 and ot.m.pinvar == 0.2 and 4 <= int(const.sum()) < ot.P
+        for a in nodes:
+            for e in triple_ref.edges_of(ot, a):
+                ot.lk(e)
+                assert np.any(ot.fact_sum_scale[const] != 0) and np.any(ot.fact_sum_scale[const] == 0), (a, e)
+        _check_synthetic(t, ot, nodes, "+I at 20 states", keep_at=1, ties=True)
+    finally:
+        t.close()
+
+
+def _outer_key(ot, a, e):
+    """the oracle's key of the vector node a reads across its edge e: the side of e away from a"""
+    return (e, 1 if a == ot.el[e] else 0)
+
+
+@pytest.mark.parametrize("name,a,other", [("nucleic_gtr_g4", 58, 70), ("proteic_lg_g4", 54, 62)])
+def test_small_floor_raises_the_candidates_own_warning(name, a, other):
+    """The outer vectors of edge positions 0 and 1 of a node with three internal neighbours rewritten (x 1e-200 at patterns 1::7, on
+    the device and in the oracle; a fresh tree, closed afterwards): those patterns are floored at SMALL in every evaluation of the
+    node's three searches.  The oracle's warning is asserted first; the record's warning is the candidate's own, and the instance's
+    flag is the LAST candidate's (include/phyhip.h)."""
+    d = _golden(name)
+    t, ot = device_tree_from_golden(d)
+    try:
+        _prepare(t, ot)
+        e = triple_ref.edges_of(ot, a)
+        mine, clean = _candidate(t, a), _candidate(t, other)
+        assert all(x >= ot.n for x in mine[0]) and other not in [v for v, _ in ot.adj[a]]
+        for i in (0, 1):
+            key = _outer_key(ot, a, e[i])
+            assert t.side_buffer(*key) == mine[0][i]
+            ot.plk[key][1::7] *= 1e-200
+            t.inst.set_partials(mine[0][i], ot.plk[key])
+        assert t.inst.numerical_warning() == 0
+        for node, want in ((a, 1), (other, 0)):          # the oracle first: Lk(b) on each of the node's edges
+            for b in triple_ref.edges_of(ot, node):
+                ot.update_partial(b, node)
+                ot.lk(b)
+                assert ot.numerical_warning == want, (name, node, b)
+        res = t.inst.optimise_triples([mine, clean, mine], keep=0)
+        assert [r.warning for r in res] == [1, 0, 1] and t.inst.numerical_warning() == 1
+        for node, c, r in zip((a, other, a), (mine, clean, mine), res):
+            replays = _staged(ot, node, c, r, (name, "SMALL floor"))
+            assert all(s.status == 0 for s in replays) or node != a, (name, [s.status for s in replays])
+        assert res[0].as_tuple() == res[2].as_tuple()
+        assert res[0].lkBegin[0] < float(d["lnL"][0]) - 600.0 * len(range(1, ot.P, 7))     # log(DBL_MIN) = -708 per floored pattern
+        _kept_vectors(t, ot, a, res[0], (name, "SMALL floor"))
+        res = t.inst.optimise_triples([mine, clean])
+        assert [r.warning for r in res] == [1, 0] and t.inst.numerical_warning() == 0
+    finally:
+        t.close()
+
+
+# ---- a candidate that stops on real sums ----------------------------------------------------------------------------------------
+def _first_search(ot, a, lens, pos=0):
+    """triple_ref's search of edge position pos of node a from `lens`, the edges before it left as they are; the oracle tree is put back"""
+    e = triple_ref.edges_of(ot, a)
+    l0 = [float(ot.len[x]) for x in e]
+    try:
+        triple_ref.restore(ot, e, lens)
+        ot.update_partial(e[pos], a)
+        return triple_ref.br_len_opt(ot, e[pos])
+    finally:
+        triple_ref.restore(ot, e, l0)
+        for x in e:
+            ot.update_partial(x, a)
+
+
+@pytest.mark.parametrize("name,a,start", [("nucleic_gtr_g4", 70, 1e308), ("nucleic_gtr_g4", 70, float("inf")), ("proteic_lg_g4", 57, 1e308)])
+def test_a_candidate_that_stops_with_no_root_of_the_spline(name, a, start):
+    """A start of 1e308 / +inf at edge position 0: the derivative is negative at l_max, the upper walk keeps v = the unclamped start,
+    the cubic's coefficients overflow and u / v falls below 0.9 -- status 3, decided on infinities.  The candidate stops there: best_l
+    so far, the two later searches not reached, nothing kept; its neighbours in the call are what they are alone.  The single-edge
+    call and the host layer's two routes stop at the same count."""
+    d = _golden(name)
+    t, ot = device_tree_from_golden(d)
+    try:
+        _prepare(t, ot)
+        x, fl, ln = _candidate(t, a)
+        lens = (start, ln[1], ln[2])
+        ref = _first_search(ot, a, lens)
+        assert ref.status == brlen_ref.NO_ROOT and ref.result.best_from != "spline" and ref.result.evaluations >= 30, (name, ref.status)
+        before, after = _candidate(t, a - 1, 20.0), _candidate(t, a + 1, 0.05)
+        whole = t.inst.optimise_triples([before, (x, fl, lens), after], keep=2)
+        r = whole[1]
+        assert tuple(r.status) == (3, -1, -1) and tuple(r.evaluations) == (ref.result.evaluations, 0, 0), (tuple(r.status), tuple(r.evaluations))
+        assert r.length[0] == ref.result.l and tuple(r.length[1:]) == tuple(lens[1:])
+        _staged(ot, a, (x, fl, lens), r, (name, "status 3"))
+        _kept_vectors(t, ot, a + 1, whole[2], (name, "kept beside a stopped candidate"))
+        whole = [w.as_tuple() for w in whole]
+        for c, got, node in ((before, whole[0], a - 1), (after, whole[2], a + 1)):
+            alone = t.inst.optimise_triples([c])[0]
+            assert alone.as_tuple() == got and got[5][2] in (0, 1, 2), (name, node, alone.as_tuple(), got)
+            _staged(ot, node, c, alone, (name, "beside a stopped candidate"))
+        t.inst.optimise_triples([before, (x, fl, lens), after], keep=1)
+        with pytest.raises(capi.PhyhipError) as ei:       # nothing is kept of a candidate that stopped
+            t.inst.triple_partials(0)
+        assert ei.value.code == capi.ERROR_OUT_OF_RANGE
+        # phyhip_optimise_edge_length from the same start on the same edge (the tree's other lengths are the candidate's)
+        e = _edges(t, a)
+        l0 = float(d["edge_len"][e[0]])
+        t.edge(e[0]).contents.l = start
+        t.Set_Update_Eigen_Lr(True); t.Set_Use_Eigen_Lr(False)
+        lkb = t.Lk(e[0])
+        t.Set_Update_Eigen_Lr(False)
+        single = t.inst.optimise_edge_length(start, lkb)
+        assert single[3:] == (r.evaluations[0], 3) and single[0] == r.length[0]
+        t.Set_Use_Eigen_Lr(False)
+        # the host layer: Br_Len_Opt on either route and Triple_Dist stop with the status's words at the same count
+        for route in (dict(force_host_chain=True), dict(force_device=True)):
+            grown = t.n_tot_bl_opt
+            with pytest.raises(capi.PhyhipError, match="no acceptable root of the spline"):
+                t.Br_Len_Opt(e[0], l=start, **route)
+            tr = t.tree.contents
+            assert (tr.bl_opt_evaluations, tr.bl_opt_status) == (r.evaluations[0], 3) and t.on_device == ("force_device" in route)
+            assert t.n_tot_bl_opt - grown == ref.result.n_tot == r.evaluations[0] - 1
+            assert t.edge(e[0]).contents.l == r.length[0]          # best_l so far; the matrix is not rebuilt
+        t.edge(e[0]).contents.l = start
+        grown = t.n_tot_bl_opt
+        with pytest.raises(capi.PhyhipError, match="no acceptable root of the spline"):
+            t.Triple_Dist(a)
+        assert t.tree.contents.bl_opt_status == 3 and t.n_tot_bl_opt - grown == r.evaluations[0] - 1
+        assert [t.edge(b).contents.l for b in e] == [r.length[0], ln[1], ln[2]]
+        t.edge(e[0]).contents.l = l0
+        t.Update_PMat_At_Given_Edge(e[0])
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("start", [float("-inf"), 0.0, -1.0])
+def test_starts_at_and_below_zero(start):
+    """-inf, 0.0 and -1.0 at edge positions 0 and 1 of nucleic_gtr_g4's node 70: at position 1 the first probe (clamped to l_min)
+    already has a negative derivative and the next length leaves [l_min, l_max] -- status 1 after one evaluation, l_out the UNCLAMPED
+    start; at position 0 the walk goes up from l_min (73 evaluations on the CPU).  The device and the chain are held to the replay."""
+    d = _golden("nucleic_gtr_g4")
+    t, ot = device_tree_from_golden(d)
+    try:
+        _prepare(t, ot)
+        a = 70
+        x, fl, ln = _candidate(t, a)
+        e = _edges(t, a)
+        for pos in (0, 1):
+            lens = tuple(start if i == pos else ln[i] for i in range(3))
+            ref = _first_search(ot, a, lens, pos) if pos == 0 else None
+            r = t.inst.optimise_triples([(x, fl, lens)], keep=0)[0]
+            replays = _staged(ot, a, (x, fl, lens), r, ("start", start, pos))
+            assert all(s in (0, 1, 2) for s in r.status), tuple(r.status)
+            if pos == 1:
+                assert (r.status[1], r.evaluations[1]) == (1, 1) and r.length[1] == start and replays[1].result.l == start
+            else:
+                assert (r.status[0], r.evaluations[0]) == (ref.status, ref.result.evaluations) and r.evaluations[0] >= 60
+            _kept_vectors(t, ot, a, r, ("start", start, pos))
+            # the chain: the host layer's Triple_Dist from the same lengths
+            for b, l in zip(e, lens):
+                t.edge(b).contents.l = l
+            lens_chain, lnl, n_tot = t.Triple_Dist(a)
+            assert n_tot == sum(ev - 1 + (1 if st in (1, 2) else 0) for ev, st in zip(r.evaluations, r.status)), (start, pos, n_tot)
+            assert lens_chain[pos] == r.length[pos] or replays[pos].result.best_from == "spline"
+            if pos == 1:
+                assert lens_chain[1] == start
+            for b in e:
+                t.edge(b).contents.l = float(d["edge_len"][b])
+                t.Update_PMat_At_Given_Edge(b)
+            for b in e:
+                t.Update_Partial_Lk(b, a)
+    finally:
+        t.close()
+
+
+# ---- the documented maximum -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ns", [4, 20])
+def test_the_documented_maximum_of_patterns(ns):
+    """capi.TRIPLE_MAX_PATTERNS patterns, 8 categories: one candidate at scale 1.0 (the bounds from the last two probes, as above 64
+    patterns everywhere), and the chunk bound for one candidate at this size"""
+    assert capi.TRIPLE_MAX_PATTERNS == 16384
+    t, ot, tree, st = synthetic_pair(6, 16384, ns, 8, seed=3)
+    try:
+        _check_synthetic(t, ot, (7,), ("maximum", ns), scales=(1.0,))
+        pe = (ot.P + 1) // 2 * 2
+        fixed = (3 * (ot.P * ot.m.ncatg * ot.m.ns * 8 + pe * 4) + 255) // 256 * 256
+        per = (3 * ot.m.ncatg * ot.m.ns ** 2 + ot.P * ot.m.ncatg * ot.m.ns) * 8 + pe * 4 + 136
+        assert capi.triple_chunk_candidates(ot.P, ot.m.ncatg, ot.m.ns, fixed + per) == 1
+        assert capi.triple_chunk_candidates(ot.P, ot.m.ncatg, ot.m.ns, fixed + 2 * per) == 2
+        cands = [_candidate(t, 7), _candidate(t, 8)]
+        whole = [r.as_tuple() for r in t.inst.optimise_triples(cands)]
+        t.inst.set_triple_work_space(fixed + per)          # one candidate per chunk
+        try:
+            assert [r.as_tuple() for r in t.inst.optimise_triples(cands, keep=1)] == whole
+        finally:
+            t.inst.set_triple_work_space(0)
     finally:
         t.close()
 
