@@ -1202,7 +1202,7 @@ int phyhip_synchronize(int instance)
   GET_INST(I, instance);
   int rc = pars_flush_queue(I);
   if (rc == 0) rc = flush_sync(I);
-  if (rc == 0) { I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch; } // nothing queued is left
+  if (rc == 0) side_stream_drained(I); // nothing queued is left
   return rc;
 }
 

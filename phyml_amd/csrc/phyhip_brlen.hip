@@ -193,9 +193,7 @@ static int brlen_run(Instance *I, double *l, double initLnL, int iterMax, double
   if ((rc = tm.mark())) return rc;
   HIPCHK(hipStreamSynchronize(I->stream)); // (the record is in host memory once the kernel has ended)
   if ((rc = tm.toc(U.prof_ms))) return rc;
-  // the stream has drained: clean at once, as after a fenced evaluation (phyhip_queue.hip) -- the dLk calls that follow can be served
-  // resident again
-  I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch;
+  side_stream_drained(I); // the dLk calls that follow can be served resident again
   if (h->status < 0) return fail(PHYHIP_ERROR_GENERAL, "%s: the search finished without handing its result over", who);
   res = *h;
   if (I->prof)

@@ -21,6 +21,9 @@
 //                        searches in sequence (one kernel, entry points of its own)
 //   phyhip_side.hpp      the host layer those last eight share (host code only): the work space grown on use, the walk over the plain
 //                        instance or every shard, the refusals by kind of instance, the kernel timer, Instance::side
+//   phyhip_scan_plan.hpp the planning of the calls that run a list of candidates in chunks (the two regraft scans, Triple_Dist): chunk
+//                        size, the work-space layouts as data, the distinct-length slot table, record packing.  Plain host C++, no HIP
+//   phyhip_scan.hpp      their host driver: candidate checks, work-space reservation, the chunk walk, the scans' chunk loop
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor

@@ -28,15 +28,17 @@
 // loops over the classes and combines them as MIXT_Lk does (mixregraft_matrices_kernel, mixregraft_classes_kernel; their header
 // stands in front of them).  Operand fetch, joined vector, product and the matrix body are device functions both scans call
 // (phyhip_regraft_dev.hpp, which phyhip_triple.hip includes too).
+// Host side: each scan brings its refusals, its kernel parameters and its kernels; the candidate checks, the reservation and the chunk
+// loop are phyhip_scan.hpp's, every offset and the chunk size phyhip_scan_plan.hpp's (ScanLayout, left on the unit for the getters).
 #include <memory>
 
 #include "phyhip_regraft_dev.hpp" // the matrix body, operand fetch, joined vector and product: shared with phyhip_triple.hip
+#include "phyhip_scan.hpp"        // the host driver: candidate checks, work-space reservation, the chunk loop
 
 namespace phyhip_host
 {
 
 constexpr int kRegraftMaxCategories = 8; // the 4-state kernel holds C * S values in registers
-constexpr int kRegraftTile = 256;
 
 struct RegraftPmatParams
 {
@@ -278,6 +280,7 @@ struct MixRegraftHead
   double       pi_inv[20]; // frequencies of the invariant class
 };
 static_assert(sizeof(MixRegraftHead) == 200, "the head in front of the per-class table");
+static_assert(sizeof(MixRegraftHead) == kMixRegraftHeadBytes && sizeof(MixRegraftClass) == kMixRegraftClassBytes, "as phyhip_scan_plan.hpp places them");
 
 struct MixRegraftPmatParams
 {
@@ -429,14 +432,20 @@ template <int S, int L> __global__ __launch_bounds__(256) void mixregraft_classe
   if (threadIdx.x == 0) q.tile_sums[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
-// bytes of the work space one candidate of a chunk takes (its three matrices, tile sums, record, lengths, sum and flag) ...
-static size_t regraft_candidate_bytes(const Instance *I)
+// What scan_chunks (phyhip_scan.hpp) calls per chunk, for either scan: the matrix kernel over (distinct lengths, matrices per slot),
+// the scan kernel over (tiles, candidates), the sums.  PQ / Q: the two parameter structs of the scan; they name these members alike.
+template <class PQ, class Q>
+static auto scan_launcher(hipStream_t stream, void (*pmat)(PQ), void (*scan)(Q), PQ &pq, Q &q, int per_slot, size_t tiles)
 {
-  const size_t tiles = (size_t)((I->P + kRegraftTile - 1) / kRegraftTile);
-  return 3 * (size_t)I->C * I->S * I->S * sizeof(double) + tiles * sizeof(double) + sizeof(RegraftRec) + 3 * sizeof(double) + sizeof(double) + 8;
+  return [=, &pq, &q](size_t n, size_t n_lengths, int keep_cand, const RegraftRec *d_recs, const double *d_lengths, int *d_flags, double *d_out) {
+    q.recs = d_recs; q.keep_cand = keep_cand;
+    pq.lengths = d_lengths; pq.flags = d_flags; pq.n_flags = (int)n;
+    hipLaunchKernelGGL(pmat, dim3((unsigned)n_lengths, (unsigned)per_slot), dim3(256), 0, stream, pq);
+    hipLaunchKernelGGL(scan, dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, stream, q);
+    hipLaunchKernelGGL(regraft_sum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, (const double *)q.tile_sums, d_out, (int)tiles, (int)n);
+    return 0;
+  };
 }
-// ... and of the kept vector with its exponents, which every call's layout reserves
-static size_t regraft_keep_bytes(const Instance *I) { return (size_t)I->P * I->C * I->S * sizeof(double) + (((size_t)I->P + 1) & ~(size_t)1) * sizeof(int); }
 
 // One plain instance: its patterns of every candidate.  sums[k] / warns[k] receive this instance's share.
 static int regraft_run(Instance *I, int eigen, const phyhip_regraft_candidate *cand, int count, int keep, double *sums, int *warns)
@@ -446,141 +455,35 @@ static int regraft_run(Instance *I, int eigen, const phyhip_regraft_candidate *c
   if ((rc = refuse_kind(I, who, kRefuseRank | kRefuseClassAxis | kRefuseGenericLoop | kRefuseStates))) return rc;
   if (I->C < 1 || I->C > kRegraftMaxCategories) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for %d categories", who, I->C);
   if (eigen < 0 || eigen >= I->NE) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: eigenIndex %d (0..%d)", who, eigen, I->NE - 1);
-  for (int k = 0; k < count; ++k)
-  {
-    const phyhip_regraft_candidate &c = cand[k];
-    if ((rc = check_partial_index(I, c.child1Partials, true)) || (rc = check_partial_index(I, c.child2Partials, true)) ||
-        (rc = check_partial_index(I, c.subtreePartials, true)))
-      return fail(rc, "%s: candidate %d: %s", who, k, std::string(g_err).c_str());
-    if ((c.flags & PHYHIP_REGRAFT_SUBTREE_IS_LEFT) && c.subtreePartials < I->tips)
-      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d: tip %d as the left operand", who, k, c.subtreePartials);
-  }
-  auto &U = side_of(I).regraft;
+  if ((rc = regraft_check_candidates(I, cand, count, who))) return rc;
+  RegraftUnit &U = side_of(I).regraft;
   U.valid = false;
-  for (int k = 0; k < count; ++k)
-  {
-    devirtualise(I, cand[k].child1Partials); devirtualise(I, cand[k].child2Partials); devirtualise(I, cand[k].subtreePartials);
-  }
-  if ((rc = flush_sync(I))) return rc; // (queued matrix work and partial updates first: the path updates of the caller are seen)
-  if ((rc = upload_masks(I))) return rc;
-
-  const size_t SS = (size_t)I->S * I->S, MS = (size_t)I->C * SS, tiles = (size_t)((I->P + kRegraftTile - 1) / kRegraftTile);
-  const size_t per = regraft_candidate_bytes(I), fixed = regraft_keep_bytes(I);
-  size_t       chunk = U.max_bytes > fixed + per ? (U.max_bytes - fixed) / per : 1;
-  chunk = std::min(chunk, std::min((size_t)count, (size_t)65535)); // (a grid's second dimension holds 65535 candidates)
-  if ((rc = U.work.reserve(fixed + chunk * per, who))) return rc;
-  // layout: kept vector | its exponents | matrices | of a launch of n: tile sums, flags (8 bytes per candidate), sums | records, lengths
-  // (what goes up is one copy, what comes down is one copy)
-  RegraftParams q;
+  if ((rc = regraft_make_real(I, cand, count))) return rc;
+  if ((rc = scan_reserve(U, I, I->C, 0, count, who))) return rc;
+  const ScanLayout &L = U.lay;
+  const size_t      SS = (size_t)I->S * I->S;
+  RegraftParams     q;
   memset(&q, 0, sizeof q);
-  q.keep = (double *)U.work.ptr;
-  double *d_mats = (double *)((char *)U.work.ptr + fixed);
-  q.mats = d_mats;
-  q.tile_sums = d_mats + 3 * chunk * MS;
-  RegraftRec *d_recs = (RegraftRec *)(q.tile_sums + chunk * tiles + 2 * chunk);
-  q.recs = d_recs;
+  q.keep = U.work.at<double>(L.keep); q.mats = U.work.at<double>(L.mats); q.tile_sums = U.work.at<double>(L.tile_sums);
   q.tip_codes = I->d_tipcodes; q.code_masks = I->d_masks; q.wght = I->d_wght; q.pi = I->d_pi; q.cat_w = I->d_catw; q.invar = I->invar_model ? I->d_invar : nullptr;
   q.partials = I->d_partials; q.scales = I->d_scales;
   q.P = I->P; q.Ppad = I->Ppad; q.C = I->C; q.tips = I->tips;
   q.apply_scaling = I->apply_scaling; q.pinvar = I->pinvar;
   RegraftPmatParams pq;
   memset(&pq, 0, sizeof pq);
-  pq.mats = d_mats; pq.C = I->C;
+  pq.mats = U.work.at<double>(L.mats); pq.C = I->C;
   pq.U = I->d_evec + (size_t)eigen * SS; pq.V = I->d_ivec + (size_t)eigen * SS; pq.R = I->d_eval + (size_t)eigen * I->S; pq.rates = I->d_catr;
   pq.br_len_mult = I->br_len_mult; pq.l_min = I->l_min; pq.l_max = I->l_max;
-
-  std::vector<RegraftRec> recs;
-  std::vector<double>     lens;
-  std::vector<char>       up;
-  std::vector<double>     down;
-  std::unordered_map<unsigned long long, int> slot_of; // a length's bits -> its matrix slot: identical lengths of a chunk are built once
-  auto slot = [&](double l) {
-    unsigned long long bits;
-    memcpy(&bits, &l, sizeof bits);
-    const auto it = slot_of.find(bits);
-    if (it != slot_of.end()) return it->second;
-    lens.push_back(l);
-    return slot_of[bits] = (int)lens.size() - 1;
-  };
-  SideTimer tm(I);
-  U.chunks = 0;
-  for (size_t first = 0; first < (size_t)count; first += chunk)
-  {
-    const size_t n = std::min(chunk, (size_t)count - first);
-    recs.clear(); lens.clear(); slot_of.clear();
-    for (size_t k = 0; k < n; ++k)
-    {
-      const phyhip_regraft_candidate &c = cand[first + k];
-      recs.push_back(RegraftRec{c.child1Partials, c.child2Partials, c.subtreePartials, c.flags, slot(c.child1Length), slot(c.child2Length),
-                                slot(c.subtreeLength), 0});
-    }
-    up.resize(n * sizeof(RegraftRec) + lens.size() * sizeof(double));
-    memcpy(up.data(), recs.data(), n * sizeof(RegraftRec));
-    memcpy(up.data() + n * sizeof(RegraftRec), lens.data(), lens.size() * sizeof(double));
-    HIPCHK(hipMemcpyAsync(d_recs, up.data(), up.size(), hipMemcpyHostToDevice, I->stream));
-    pq.lengths = (const double *)(d_recs + n);
-    double *const d_down = q.tile_sums + n * tiles; // (where the scan kernel of a launch of n candidates looks for its flags)
-    double *const d_out = d_down + n;
-    pq.flags = (int *)d_down; pq.n_flags = (int)n;
-    q.keep_cand = (keep >= (int)first && keep < (int)(first + n)) ? keep - (int)first : -1;
-    if ((rc = tm.tic())) return rc;
-    const dim3 pgrid((unsigned)lens.size(), (unsigned)I->C), sgrid((unsigned)tiles, (unsigned)n), block(256);
-    const int layout = layout_of(I);
-    if (I->S == 4)
-    {
-      hipLaunchKernelGGL(regraft_pmat_kernel<4>, pgrid, block, 0, I->stream, pq);
-      if (layout == 2) hipLaunchKernelGGL((regraft_scan_kernel<4, 2>), sgrid, block, 0, I->stream, q);
-      else hipLaunchKernelGGL((regraft_scan_kernel<4, 0>), sgrid, block, 0, I->stream, q);
-    }
-    else
-    {
-      hipLaunchKernelGGL(regraft_pmat_kernel<20>, pgrid, block, 0, I->stream, pq);
-      if (layout == 1) hipLaunchKernelGGL((regraft_scan_kernel<20, 1>), sgrid, block, 0, I->stream, q);
-      else hipLaunchKernelGGL((regraft_scan_kernel<20, 0>), sgrid, block, 0, I->stream, q);
-    }
-    hipLaunchKernelGGL(regraft_sum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, I->stream, (const double *)q.tile_sums, d_out, (int)tiles,
-                       (int)n);
-    HIPCHK(hipGetLastError());
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(I->stream));
-    if ((rc = tm.toc(U.prof_ms))) return rc;
-    down.resize(2 * n);
-    HIPCHK(hipMemcpy(down.data(), d_down, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
-    memcpy(sums + first, down.data() + n, n * sizeof(double));
-    for (size_t k = 0; k < n; ++k) warns[first + k] = reinterpret_cast<const int *>(down.data())[k] ? 1 : 0;
-    ++U.chunks;
-    U.last_first = (int)first;
-  }
-  // the last chunk's matrices stay in the work space for phyhip_get_regraft_transition_matrix
-  U.last_slots.resize(recs.size() * 3);
-  for (size_t k = 0; k < recs.size(); ++k)
-  {
-    U.last_slots[3 * k] = recs[k].m1; U.last_slots[3 * k + 1] = recs[k].m2; U.last_slots[3 * k + 2] = recs[k].m3;
-  }
-  U.last_count = count; U.last_keep = keep; U.valid = true;
-  if (I->prof)
-  {
-    ++U.prof_n;
-    U.prof_cand += count;
-  }
-  // the stream has drained: clean at once -- the Lk(b) / dLk calls that follow can be served resident again
-  I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch;
+  const int  layout = layout_of(I);
+  void (*pmat)(RegraftPmatParams) = regraft_pmat_kernel<4>;
+  void (*scan)(RegraftParams) = layout == 2 ? regraft_scan_kernel<4, 2> : regraft_scan_kernel<4, 0>;
+  if (I->S == 20) pmat = regraft_pmat_kernel<20>, scan = layout == 1 ? regraft_scan_kernel<20, 1> : regraft_scan_kernel<20, 0>;
+  if ((rc = scan_chunks(U, I, cand, count, keep, sums, warns, nullptr, scan_launcher(I->stream, pmat, scan, pq, q, I->C, L.tiles)))) return rc;
+  side_stream_drained(I); // the Lk(b) / dLk calls that follow can be served resident again
   return PHYHIP_SUCCESS;
 }
 
 // ---- the mixture scan's host side ----------------------------------------------------------------------------------------------------
-static size_t mixregraft_exponent_ints(const Instance *I) { return ((size_t)I->P + 1) & ~(size_t)1; }
-// bytes of the work space one candidate of a chunk takes over n classes ...
-static size_t mixregraft_candidate_bytes(const Instance *I, int n)
-{
-  const size_t tiles = (size_t)((I->P + kRegraftTile - 1) / kRegraftTile);
-  return 3 * (size_t)n * I->S * I->S * sizeof(double) + tiles * sizeof(double) + sizeof(RegraftRec) + 3 * sizeof(double) + sizeof(double) + 8;
-}
-// ... and of the kept vectors with their exponents and the per-class table, which every call's layout reserves
-static size_t mixregraft_keep_bytes(const Instance *I, int n) { return (size_t)n * ((size_t)I->P * I->S * sizeof(double) + mixregraft_exponent_ints(I) * sizeof(int)); }
-static size_t mixregraft_table_bytes(int n) { return sizeof(MixRegraftHead) + (size_t)n * sizeof(MixRegraftClass); } // (the head in front of the table)
-static size_t mixregraft_fixed_bytes(const Instance *I, int n) { return mixregraft_keep_bytes(I, n) + mixregraft_table_bytes(n); }
-
 struct MixRegraftCoef
 {
   const double *proba, *r_w, *e_w;
@@ -614,48 +517,17 @@ static int mixregraft_run(const int *ids, int n_cls, const int *eigen, const phy
       return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d: another pattern count, state count, buffer layout or device than class 0", who, k);
     if (eigen[k] < 0 || eigen[k] >= I->NE) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d: eigenIndex %d (0..%d)", who, k, eigen[k], I->NE - 1);
   }
-  for (int k = 0; k < count; ++k)
-  {
-    const phyhip_regraft_candidate &c = cand[k];
-    if ((rc = check_partial_index(I0, c.child1Partials, true)) || (rc = check_partial_index(I0, c.child2Partials, true)) ||
-        (rc = check_partial_index(I0, c.subtreePartials, true)))
-      return fail(rc, "%s: candidate %d: %s", who, k, std::string(g_err).c_str());
-    if ((c.flags & PHYHIP_REGRAFT_SUBTREE_IS_LEFT) && c.subtreePartials < I0->tips)
-      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d: tip %d as the left operand", who, k, c.subtreePartials);
-  }
-  auto &U = side_of(I0).mixregraft;
+  if ((rc = regraft_check_candidates(I0, cand, count, who))) return rc;
+  RegraftUnit &U = side_of(I0).mixregraft;
   U.valid = false;
-  // every class: the buffers a record names stored, queued matrix work and partial updates run (the path updates of the caller are
-  // seen), its stream drained -- all of it before anything is launched
+  // every class: its buffers real, its queue run, its stream drained -- all of it before anything is launched
   for (Instance *I : cls)
-  {
-    for (int k = 0; k < count; ++k)
-    {
-      devirtualise(I, cand[k].child1Partials); devirtualise(I, cand[k].child2Partials); devirtualise(I, cand[k].subtreePartials);
-    }
-    if ((rc = flush_sync(I))) return rc;
-    if ((rc = upload_masks(I))) return rc;
-  }
-
-  const size_t SS = (size_t)I0->S * I0->S, MS = (size_t)n_cls * SS, tiles = (size_t)((I0->P + kRegraftTile - 1) / kRegraftTile);
-  const size_t per = mixregraft_candidate_bytes(I0, n_cls), fixed = mixregraft_fixed_bytes(I0, n_cls);
-  size_t       chunk = U.max_bytes > fixed + per ? (U.max_bytes - fixed) / per : 1;
-  chunk = std::min(chunk, std::min((size_t)count, (size_t)65535)); // (a grid's second dimension holds 65535 candidates)
-  if ((rc = U.work.reserve(fixed + chunk * per, who))) return rc;
-  // layout: kept vectors | their exponents | matrices | of a launch of n: tile sums, flags (8 bytes per candidate), sums | class table,
-  // records, lengths (what goes up is one copy, what comes down is one copy)
-  MixRegraftParams q;
-  memset(&q, 0, sizeof q);
-  q.keep = (double *)U.work.ptr;
-  double *d_mats = (double *)((char *)U.work.ptr + mixregraft_keep_bytes(I0, n_cls));
-  q.mats = d_mats;
-  q.tile_sums = d_mats + 3 * chunk * MS;
-  MixRegraftHead  *d_head = (MixRegraftHead *)(q.tile_sums + chunk * tiles + 2 * chunk);
-  MixRegraftClass *d_cls = (MixRegraftClass *)(d_head + 1);
-  RegraftRec      *d_recs = (RegraftRec *)(d_cls + n_cls);
-  q.head = d_head; q.cls = d_cls; q.recs = d_recs;
-  q.wght = I0->d_wght;
-  q.P = I0->P; q.Ppad = I0->Ppad; q.n_cls = n_cls; q.tips = I0->tips;
+    if ((rc = regraft_make_real(I, cand, count))) return rc;
+  if ((rc = scan_reserve(U, I0, n_cls, n_cls, count, who))) return rc;
+  U.classes = n_cls;
+  const ScanLayout &L = U.lay;
+  // the head and the per-class table: they go up in front of every chunk's records
+  const size_t SS = (size_t)I0->S * I0->S;
   MixRegraftHead head;
   memset(&head, 0, sizeof head);
   head.r_sum = co.r_sum; head.e_sum = co.e_sum; head.sum_probas = co.sum_probas;
@@ -673,91 +545,119 @@ static int mixregraft_run(const int *ids, int n_cls, const int *eigen, const phy
     t.proba = co.proba[k]; t.r_w = co.r_w[k]; t.e_w = co.e_w[k];
     t.apply_scaling = I->apply_scaling;
   }
+  std::vector<char> prefix(L.prefix_bytes);
+  memcpy(prefix.data(), &head, sizeof head);
+  memcpy(prefix.data() + sizeof head, table.data(), (size_t)n_cls * sizeof(MixRegraftClass));
+  MixRegraftParams q;
+  memset(&q, 0, sizeof q);
+  q.keep = U.work.at<double>(L.keep); q.mats = U.work.at<double>(L.mats); q.tile_sums = U.work.at<double>(L.tile_sums);
+  q.head = U.work.at<MixRegraftHead>(L.prefix); q.cls = U.work.at<MixRegraftClass>(L.prefix + sizeof head);
+  q.wght = I0->d_wght;
+  q.P = I0->P; q.Ppad = I0->Ppad; q.n_cls = n_cls; q.tips = I0->tips;
   MixRegraftPmatParams pq;
   memset(&pq, 0, sizeof pq);
-  pq.mats = d_mats; pq.cls = d_cls; pq.n_cls = n_cls;
+  pq.mats = U.work.at<double>(L.mats); pq.cls = q.cls; pq.n_cls = n_cls;
+  void (*pmat)(MixRegraftPmatParams) = mixregraft_matrices_kernel<4>;
+  void (*scan)(MixRegraftParams) = layout == 2 ? mixregraft_classes_kernel<4, 2> : mixregraft_classes_kernel<4, 0>;
+  if (I0->S == 20) pmat = mixregraft_matrices_kernel<20>, scan = layout == 1 ? mixregraft_classes_kernel<20, 1> : mixregraft_classes_kernel<20, 0>;
+  if ((rc = scan_chunks(U, I0, cand, count, keep, sums, warns, prefix.data(), scan_launcher(I0->stream, pmat, scan, pq, q, n_cls, L.tiles)))) return rc;
+  for (Instance *I : cls) side_stream_drained(I); // every stream has drained
+  return PHYHIP_SUCCESS;
+}
 
-  std::vector<RegraftRec> recs;
-  std::vector<double>     lens;
-  std::vector<char>       up;
-  std::vector<double>     down;
-  std::unordered_map<unsigned long long, int> slot_of; // a length's bits -> its matrix slot: identical lengths of a chunk are built once per class
-  auto slot = [&](double l) {
-    unsigned long long bits;
-    memcpy(&bits, &l, sizeof bits);
-    const auto it = slot_of.find(bits);
-    if (it != slot_of.end()) return it->second;
-    lens.push_back(l);
-    return slot_of[bits] = (int)lens.size() - 1;
-  };
-  SideTimer tm(I0);
-  U.chunks = 0;
-  const size_t tb = mixregraft_table_bytes(n_cls);
-  for (size_t first = 0; first < (size_t)count; first += chunk)
+// ---- what the entry points of the two scans share -------------------------------------------------------------------------------------
+// a candidate's shard sums are added in shard order, its warnings ORed
+struct __attribute__((visibility("hidden"))) ShardSums
+{
+  std::vector<double> part, sum;
+  std::vector<int>    wpart, warn;
+  explicit ShardSums(int count) : part((size_t)count), sum((size_t)count, 0.0), wpart((size_t)count), warn((size_t)count, 0) {}
+  void add() { for (size_t k = 0; k < sum.size(); ++k) sum[k] += part[k], warn[k] |= wpart[k]; } // the shard that has just run
+  void hand_over(double *outLogLikelihoods, int *outWarnings) const
   {
-    const size_t n = std::min(chunk, (size_t)count - first);
-    recs.clear(); lens.clear(); slot_of.clear();
-    for (size_t k = 0; k < n; ++k)
-    {
-      const phyhip_regraft_candidate &c = cand[first + k];
-      recs.push_back(RegraftRec{c.child1Partials, c.child2Partials, c.subtreePartials, c.flags, slot(c.child1Length), slot(c.child2Length),
-                                slot(c.subtreeLength), 0});
-    }
-    up.resize(tb + n * sizeof(RegraftRec) + lens.size() * sizeof(double));
-    memcpy(up.data(), &head, sizeof head);
-    memcpy(up.data() + sizeof head, table.data(), (size_t)n_cls * sizeof(MixRegraftClass));
-    memcpy(up.data() + tb, recs.data(), n * sizeof(RegraftRec));
-    memcpy(up.data() + tb + n * sizeof(RegraftRec), lens.data(), lens.size() * sizeof(double));
-    HIPCHK(hipMemcpyAsync(d_head, up.data(), up.size(), hipMemcpyHostToDevice, I0->stream));
-    pq.lengths = (const double *)(d_recs + n);
-    double *const d_down = q.tile_sums + n * tiles; // (where the scan kernel of a launch of n candidates looks for its flags)
-    double *const d_out = d_down + n;
-    pq.flags = (int *)d_down; pq.n_flags = (int)n;
-    q.keep_cand = (keep >= (int)first && keep < (int)(first + n)) ? keep - (int)first : -1;
-    if ((rc = tm.tic())) return rc;
-    const dim3 pgrid((unsigned)lens.size(), (unsigned)n_cls), sgrid((unsigned)tiles, (unsigned)n), block(256);
-    if (I0->S == 4)
-    {
-      hipLaunchKernelGGL(mixregraft_matrices_kernel<4>, pgrid, block, 0, I0->stream, pq);
-      if (layout == 2) hipLaunchKernelGGL((mixregraft_classes_kernel<4, 2>), sgrid, block, 0, I0->stream, q);
-      else hipLaunchKernelGGL((mixregraft_classes_kernel<4, 0>), sgrid, block, 0, I0->stream, q);
-    }
-    else
-    {
-      hipLaunchKernelGGL(mixregraft_matrices_kernel<20>, pgrid, block, 0, I0->stream, pq);
-      if (layout == 1) hipLaunchKernelGGL((mixregraft_classes_kernel<20, 1>), sgrid, block, 0, I0->stream, q);
-      else hipLaunchKernelGGL((mixregraft_classes_kernel<20, 0>), sgrid, block, 0, I0->stream, q);
-    }
-    hipLaunchKernelGGL(regraft_sum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, I0->stream, (const double *)q.tile_sums, d_out, (int)tiles,
-                       (int)n);
-    HIPCHK(hipGetLastError());
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(I0->stream));
-    if ((rc = tm.toc(U.prof_ms))) return rc;
-    down.resize(2 * n);
-    HIPCHK(hipMemcpy(down.data(), d_down, 2 * n * sizeof(double), hipMemcpyDeviceToHost));
-    memcpy(sums + first, down.data() + n, n * sizeof(double));
-    for (size_t k = 0; k < n; ++k) warns[first + k] = reinterpret_cast<const int *>(down.data())[k] ? 1 : 0;
-    ++U.chunks;
-    U.last_first = (int)first;
+    std::copy(sum.begin(), sum.end(), outLogLikelihoods);
+    if (outWarnings) std::copy(warn.begin(), warn.end(), outWarnings);
   }
-  // the last chunk's matrices stay in the work space for phyhip_get_mixture_regraft_transition_matrix
-  U.last_slots.resize(recs.size() * 3);
-  for (size_t k = 0; k < recs.size(); ++k)
-  {
-    U.last_slots[3 * k] = recs[k].m1; U.last_slots[3 * k + 1] = recs[k].m2; U.last_slots[3 * k + 2] = recs[k].m3;
-  }
-  U.classes = n_cls; U.last_count = count; U.last_keep = keep; U.valid = true;
-  if (I0->prof)
-  {
-    ++U.prof_n;
-    U.prof_cand += count;
-  }
-  // every stream has drained: clean at once -- the Lk(b) / dLk calls that follow can be served resident again
-  for (Instance *I : cls)
-  {
-    I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch;
-  }
+};
+
+static const char *const kScanCall = "phyhip_calculate_regraft_log_likelihoods call";
+static const char *const kMixScanCall = "phyhip_calculate_mixture_regraft_log_likelihoods call with this first instance";
+
+static int scan_left_something(const RegraftUnit &U, const char *who, const char *call)
+{
+  return U.valid && U.work.ptr ? 0 : fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no %s before it", who, call);
+}
+
+// the kept candidate's vector and exponents (of one class of a mixture scan), every shard its pattern range
+static int scan_get_partials(int instance, RegraftUnit SideUnits::*unit, const char *who, const char *call, int classIndex, double *outPartials,
+                             int *outScaleFactors)
+{
+  const bool mixture = unit == &SideUnits::mixregraft;
+  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long lo, long long) {
+    const RegraftUnit &U = side_of(I).*unit;
+    if (const int rc = scan_left_something(U, who, call)) return rc;
+    if (U.last_keep < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: the last call kept no candidate (keepCandidate -1)", who);
+    if (mixture && (classIndex < 0 || classIndex >= U.classes)) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d of %d", who, classIndex, U.classes);
+    const size_t cls = mixture ? classIndex : 0, row = (size_t)(mixture ? 1 : I->C) * I->S; // (doubles of a pattern in the caller's array)
+    if (outPartials) HIPCHK(hipMemcpy(outPartials + (size_t)lo * row, U.work.at<double>(U.lay.keep_of(cls)), U.lay.vec_bytes, hipMemcpyDeviceToHost));
+    if (outScaleFactors) HIPCHK(hipMemcpy(outScaleFactors + lo, U.work.at<int>(U.lay.exps_of(cls)), (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+  });
+}
+
+// one matrix of one candidate of the last chunk; classIndex: of a mixture scan, -1 of a plain one (all its categories)
+static int scan_get_matrix(int instance, RegraftUnit SideUnits::*unit, const char *who, const char *call, int classIndex, int candidate, int which,
+                           double *outMatrix)
+{
+  if (which < 0 || which > 2) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: which %d (0..2)", who, which);
+  if (!outMatrix) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: outMatrix is NULL", who);
+  const bool mixture = unit == &SideUnits::mixregraft;
+  bool       done = false; // (the matrices are the same on every shard: the first one answers)
+  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    if (done) return 0;
+    const RegraftUnit &U = side_of(I).*unit;
+    if (const int rc = scan_left_something(U, who, call)) return rc;
+    if (mixture && (classIndex < 0 || classIndex >= U.classes)) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d of %d", who, classIndex, U.classes);
+    if (candidate < 0 || candidate >= U.last_count) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d of %d", who, candidate, U.last_count);
+    if (candidate < U.last_first)
+      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d's matrices have left the work space (the call ran in %d chunks, the last from candidate %d)",
+                  who, candidate, U.chunks, U.last_first);
+    const size_t slot = (size_t)U.last_slots[3 * (size_t)(candidate - U.last_first) + which];
+    HIPCHK(hipMemcpy(outMatrix, U.work.at<double>(U.lay.matrix(slot, mixture ? classIndex : 0)), mixture ? U.lay.mat_bytes : U.lay.slot_bytes,
+                     hipMemcpyDeviceToHost));
+    done = true;
+    return 0;
+  });
+}
+
+static int scan_set_work_space(int instance, RegraftUnit SideUnits::*unit, const char *who, long long maxBytes)
+{
+  if (maxBytes < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: %lld bytes", who, maxBytes);
+  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    (side_of(I).*unit).max_bytes = maxBytes ? (size_t)maxBytes : kRegraftWorkBytes;
+    return 0;
+  });
+}
+
+// read and reset: the time is added over the shards; calls and candidates are the same on every shard, the first one's are taken
+static int scan_profile_read(int instance, RegraftUnit SideUnits::*unit, double *outKernelMs, int *outCalls, long long *outCandidates)
+{
+  double    ms = 0.0;
+  int       n = 0;
+  long long nc = 0;
+  bool      first = true;
+  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    RegraftUnit &U = side_of(I).*unit;
+    ms += U.prof_ms;
+    if (first) n = U.prof_n, nc = U.prof_cand;
+    first = false;
+    U.prof_ms = 0.0; U.prof_n = 0; U.prof_cand = 0;
+    return 0;
+  });
+  if (rc < 0) return rc;
+  if (outKernelMs) *outKernelMs = ms;
+  if (outCalls) *outCalls = n;
+  if (outCandidates) *outCandidates = nc;
   return PHYHIP_SUCCESS;
 }
 
@@ -787,71 +687,32 @@ int phyhip_calculate_regraft_log_likelihoods(int instance, int eigenIndex, const
     }
     return PHYHIP_SUCCESS;
   }
-  // every shard scans its pattern range; a candidate's shard sums are added here in shard order
-  std::vector<double> part((size_t)count), sum((size_t)count, 0.0);
-  std::vector<int>    wpart((size_t)count), warn((size_t)count, 0);
+  // every shard scans its pattern range
+  ShardSums s(count);
   const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
-    const int r = regraft_run(I, eigenIndex, candidates, count, keepCandidate, part.data(), wpart.data());
+    const int r = regraft_run(I, eigenIndex, candidates, count, keepCandidate, s.part.data(), s.wpart.data());
     if (r) return r;
-    for (int k = 0; k < count; ++k)
-    {
-      sum[k] += part[k];
-      warn[k] |= wpart[k];
-    }
+    s.add();
     return 0;
   });
   if (rc < 0) return rc;
-  for (int k = 0; k < count; ++k) outLogLikelihoods[k] = sum[k];
-  if (outWarnings)
-    for (int k = 0; k < count; ++k) outWarnings[k] = warn[k];
+  s.hand_over(outLogLikelihoods, outWarnings);
   return PHYHIP_SUCCESS;
 }
 
 int phyhip_get_regraft_partials(int instance, double *outPartials, int *outScaleFactors)
 {
-  static const char *const who = "phyhip_get_regraft_partials";
-  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long lo, long long) {
-    auto &U = side_of(I).regraft;
-    if (!U.valid || !U.work.ptr) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_calculate_regraft_log_likelihoods call before it", who);
-    if (U.last_keep < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: the last call kept no candidate (keepCandidate -1)", who);
-    const size_t  CS = (size_t)I->C * I->S;
-    const double *d_keep = (const double *)U.work.ptr;
-    if (outPartials) HIPCHK(hipMemcpy(outPartials + (size_t)lo * CS, d_keep, (size_t)I->P * CS * sizeof(double), hipMemcpyDeviceToHost));
-    if (outScaleFactors) HIPCHK(hipMemcpy(outScaleFactors + lo, d_keep + (size_t)I->P * CS, (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
-  });
+  return scan_get_partials(instance, &SideUnits::regraft, "phyhip_get_regraft_partials", kScanCall, -1, outPartials, outScaleFactors);
 }
 
 int phyhip_get_regraft_transition_matrix(int instance, int candidate, int which, double *outMatrix)
 {
-  static const char *const who = "phyhip_get_regraft_transition_matrix";
-  if (which < 0 || which > 2) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: which %d (0..2)", who, which);
-  if (!outMatrix) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: outMatrix is NULL", who);
-  bool done = false; // (the matrices are the same on every shard: the first one answers)
-  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
-    if (done) return 0;
-    auto &U = side_of(I).regraft;
-    if (!U.valid || !U.work.ptr) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_calculate_regraft_log_likelihoods call before it", who);
-    if (candidate < 0 || candidate >= U.last_count) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d of %d", who, candidate, U.last_count);
-    if (candidate < U.last_first)
-      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d's matrices have left the work space (the call ran in %d chunks, the last from candidate %d)",
-                  who, candidate, U.chunks, U.last_first);
-    const size_t  MS = (size_t)I->C * I->S * I->S;
-    const double *d_mats = (const double *)((const char *)U.work.ptr + regraft_keep_bytes(I));
-    HIPCHK(hipMemcpy(outMatrix, d_mats + (size_t)U.last_slots[3 * (size_t)(candidate - U.last_first) + which] * MS, MS * sizeof(double),
-                     hipMemcpyDeviceToHost));
-    done = true;
-    return 0;
-  });
+  return scan_get_matrix(instance, &SideUnits::regraft, "phyhip_get_regraft_transition_matrix", kScanCall, -1, candidate, which, outMatrix);
 }
 
 int phyhip_set_regraft_work_space(int instance, long long maxBytes)
 {
-  if (maxBytes < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_set_regraft_work_space: %lld bytes", maxBytes);
-  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
-    side_of(I).regraft.max_bytes = maxBytes ? (size_t)maxBytes : kRegraftWorkBytes;
-    return 0;
-  });
+  return scan_set_work_space(instance, &SideUnits::regraft, "phyhip_set_regraft_work_space", maxBytes);
 }
 
 int phyhip_calculate_mixture_regraft_log_likelihoods(const int *instances, int count, const int *eigenIndices,
@@ -884,141 +745,54 @@ int phyhip_calculate_mixture_regraft_log_likelihoods(const int *instances, int c
     std::vector<int> warn((size_t)candidateCount, 0);
     if (const int rc = mixregraft_run(instances, count, eigenIndices, candidates, candidateCount, keepCandidate, co, outLogLikelihoods, warn.data()))
       return rc;
-    if (outWarnings)
-      for (int k = 0; k < candidateCount; ++k) outWarnings[k] = warn[k];
+    if (outWarnings) std::copy(warn.begin(), warn.end(), outWarnings);
     return PHYHIP_SUCCESS;
   }
   // class instances that are one-process sharded instances of one shard layout: every shard scans its pattern range over its
-  // sub-instances; a candidate's shard sums are added here in shard order
+  // sub-instances
   std::vector<Group *> Gs;
   int rc = mixture_groups(instances, count, Gs);
   if (rc) return rc;
   for (Group *G : Gs)
     if ((rc = group_take_drain_error(G))) return rc;
   if (candidateCount == 0) return PHYHIP_SUCCESS;
-  std::vector<double> part((size_t)candidateCount), sum((size_t)candidateCount, 0.0);
-  std::vector<int>    wpart((size_t)candidateCount), warn((size_t)candidateCount, 0);
+  ShardSums s(candidateCount);
   for (size_t g = 0; g < G0->sub_id.size(); ++g)
   {
     int ids[kMaxMixClasses];
     for (int k = 0; k < count; ++k) ids[k] = Gs[k]->sub_id[g];
-    if ((rc = mixregraft_run(ids, count, eigenIndices, candidates, candidateCount, keepCandidate, co, part.data(), wpart.data()))) return rc;
-    for (int k = 0; k < candidateCount; ++k)
-    {
-      sum[k] += part[k];
-      warn[k] |= wpart[k];
-    }
+    if ((rc = mixregraft_run(ids, count, eigenIndices, candidates, candidateCount, keepCandidate, co, s.part.data(), s.wpart.data()))) return rc;
+    s.add();
   }
-  for (int k = 0; k < candidateCount; ++k) outLogLikelihoods[k] = sum[k];
-  if (outWarnings)
-    for (int k = 0; k < candidateCount; ++k) outWarnings[k] = warn[k];
+  s.hand_over(outLogLikelihoods, outWarnings);
   return PHYHIP_SUCCESS;
 }
 
 int phyhip_get_mixture_regraft_partials(int firstInstance, int classIndex, double *outPartials, int *outScaleFactors)
 {
-  static const char *const who = "phyhip_get_mixture_regraft_partials";
-  return side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long lo, long long) {
-    auto &U = side_of(I).mixregraft;
-    if (!U.valid || !U.work.ptr)
-      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_calculate_mixture_regraft_log_likelihoods call with this first instance before it", who);
-    if (U.last_keep < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: the last call kept no candidate (keepCandidate -1)", who);
-    if (classIndex < 0 || classIndex >= U.classes) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d of %d", who, classIndex, U.classes);
-    const size_t  PS = (size_t)I->P * I->S;
-    const double *d_keep = (const double *)U.work.ptr;
-    const int    *d_exp = reinterpret_cast<const int *>(d_keep + (size_t)U.classes * PS) + (size_t)classIndex * mixregraft_exponent_ints(I);
-    if (outPartials) HIPCHK(hipMemcpy(outPartials + (size_t)lo * I->S, d_keep + (size_t)classIndex * PS, PS * sizeof(double), hipMemcpyDeviceToHost));
-    if (outScaleFactors) HIPCHK(hipMemcpy(outScaleFactors + lo, d_exp, (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
-    return 0;
-  });
+  return scan_get_partials(firstInstance, &SideUnits::mixregraft, "phyhip_get_mixture_regraft_partials", kMixScanCall, classIndex, outPartials,
+                           outScaleFactors);
 }
 
 int phyhip_get_mixture_regraft_transition_matrix(int firstInstance, int classIndex, int candidate, int which, double *outMatrix)
 {
-  static const char *const who = "phyhip_get_mixture_regraft_transition_matrix";
-  if (which < 0 || which > 2) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: which %d (0..2)", who, which);
-  if (!outMatrix) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: outMatrix is NULL", who);
-  bool done = false; // (the matrices are the same on every shard: the first one answers)
-  return side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long, long long) {
-    if (done) return 0;
-    auto &U = side_of(I).mixregraft;
-    if (!U.valid || !U.work.ptr)
-      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_calculate_mixture_regraft_log_likelihoods call with this first instance before it", who);
-    if (classIndex < 0 || classIndex >= U.classes) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: class %d of %d", who, classIndex, U.classes);
-    if (candidate < 0 || candidate >= U.last_count) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d of %d", who, candidate, U.last_count);
-    if (candidate < U.last_first)
-      return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate %d's matrices have left the work space (the call ran in %d chunks, the last from candidate %d)",
-                  who, candidate, U.chunks, U.last_first);
-    const size_t  SS = (size_t)I->S * I->S;
-    const double *d_mats = (const double *)((const char *)U.work.ptr + mixregraft_keep_bytes(I, U.classes));
-    const size_t  slot = (size_t)U.last_slots[3 * (size_t)(candidate - U.last_first) + which];
-    HIPCHK(hipMemcpy(outMatrix, d_mats + (slot * U.classes + classIndex) * SS, SS * sizeof(double), hipMemcpyDeviceToHost));
-    done = true;
-    return 0;
-  });
+  return scan_get_matrix(firstInstance, &SideUnits::mixregraft, "phyhip_get_mixture_regraft_transition_matrix", kMixScanCall, classIndex, candidate,
+                         which, outMatrix);
 }
 
 int phyhip_set_mixture_regraft_work_space(int firstInstance, long long maxBytes)
 {
-  if (maxBytes < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_set_mixture_regraft_work_space: %lld bytes", maxBytes);
-  return side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long, long long) {
-    side_of(I).mixregraft.max_bytes = maxBytes ? (size_t)maxBytes : kRegraftWorkBytes;
-    return 0;
-  });
+  return scan_set_work_space(firstInstance, &SideUnits::mixregraft, "phyhip_set_mixture_regraft_work_space", maxBytes);
 }
 
 int phyhip_profile_read_mixture_regraft(int firstInstance, double *outKernelMs, int *outCalls, long long *outCandidates)
 {
-  double    ms = 0.0;
-  int       n = 0;
-  long long nc = 0;
-  bool      first = true; // (calls and candidates are the same on every shard; the time is added over the shards)
-  const int rc = side_each<kSideDrain, kSideCall>(firstInstance, [&](Instance *I, long long, long long) {
-    auto &U = side_of(I).mixregraft;
-    ms += U.prof_ms;
-    if (first)
-    {
-      n = U.prof_n;
-      nc = U.prof_cand;
-    }
-    first = false;
-    U.prof_ms = 0.0;
-    U.prof_n = 0;
-    U.prof_cand = 0;
-    return 0;
-  });
-  if (rc < 0) return rc;
-  if (outKernelMs) *outKernelMs = ms;
-  if (outCalls) *outCalls = n;
-  if (outCandidates) *outCandidates = nc;
-  return PHYHIP_SUCCESS;
+  return scan_profile_read(firstInstance, &SideUnits::mixregraft, outKernelMs, outCalls, outCandidates);
 }
 
 int phyhip_profile_read_regraft(int instance, double *outKernelMs, int *outCalls, long long *outCandidates)
 {
-  double    ms = 0.0;
-  int       n = 0;
-  long long nc = 0;
-  bool      first = true; // (calls and candidates are the same on every shard; the time is added over the shards)
-  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
-    auto &U = side_of(I).regraft;
-    ms += U.prof_ms;
-    if (first)
-    {
-      n = U.prof_n;
-      nc = U.prof_cand;
-    }
-    first = false;
-    U.prof_ms = 0.0;
-    U.prof_n = 0;
-    U.prof_cand = 0;
-    return 0;
-  });
-  if (rc < 0) return rc;
-  if (outKernelMs) *outKernelMs = ms;
-  if (outCalls) *outCalls = n;
-  if (outCandidates) *outCandidates = nc;
-  return PHYHIP_SUCCESS;
+  return scan_profile_read(instance, &SideUnits::regraft, outKernelMs, outCalls, outCandidates);
 }
 
 } // extern "C"

@@ -4,17 +4,12 @@
 // plain structs it reads; no kernels.
 #pragma once
 #include "phyhip_side.hpp"
+#include "phyhip_scan_plan.hpp" // RegraftRec, the record a scan kernel reads
 #include "phyhip_layout.hpp"
 #include "phyhip_log.hpp"
 
 namespace phyhip_host
 {
-
-struct RegraftRec
-{
-  int c1, c2, sub, flags; // partials buffer or tip index of the two children and the subtree; PHYHIP_REGRAFT_*
-  int m1, m2, m3, pad;    // the three matrices: slots of the chunk's matrix area
-};
 
 // what site_tail reads (phyhip_tail.hpp); the per-site outputs are not stored
 struct RegraftTailQ

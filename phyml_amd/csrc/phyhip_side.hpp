@@ -1,8 +1,11 @@
 // phyhip_side.hpp -- the host layer of the units beside the hot path (phyhip_exact.hip, phyhip_ancestral.hip, phyhip_dist.hip,
 // phyhip_support.hip, phyhip_pars.hip, phyhip_brlen.hip, phyhip_regraft.hip, phyhip_triple.hip): a work space grown on use, the walk over the plain instance or every shard, the refusals
 // by kind of instance, the kernel timer of a profiled instance, and what those units keep on the instance.  Host code only.
+// The calls that run a list of candidates in chunks take their work-space layouts from phyhip_scan_plan.hpp and their chunk loop
+// from phyhip_scan.hpp.
 #pragma once
 #include "phyhip_host.hpp"
+#include "phyhip_scan_plan.hpp"
 
 #pragma GCC visibility push(hidden) // (inline functions of this header stay out of the library's dynamic symbols)
 namespace phyhip_host
@@ -26,6 +29,7 @@ struct WorkSpace
   void  *ptr = nullptr;
   size_t cap = 0;
   bool   holds(size_t bytes) const { return ptr && cap >= bytes; } // (false: reserve() will free and allocate)
+  template <class T> T *at(size_t byte_offset) const { return reinterpret_cast<T *>(static_cast<char *>(ptr) + byte_offset); }
   // grow-only; what it held is NOT kept.  Empty afterwards where the allocation failed.
   int reserve(size_t bytes, const char *who)
   {
@@ -161,6 +165,22 @@ struct SideTimer
 constexpr size_t kDistBandBytes = 128u << 20; // pairwise distances: the raw counts of one band of taxa stay below this by default
 constexpr size_t kRegraftWorkBytes = kDistBandBytes; // regraft scans (plain and mixture): the work space stays below this by default (a longer list runs in chunks)
 
+// a regraft scan, plain or mixture
+struct RegraftUnit
+{
+  WorkSpace  work;                          // as `lay` places it
+  ScanLayout lay;                           // of the last call (phyhip_scan_plan.hpp): the getters read through it
+  size_t     max_bytes = kRegraftWorkBytes; // the bound on the work space (phyhip_set_regraft_work_space, phyhip_set_mixture_regraft_work_space)
+  bool       valid = false;                 // a call has completed: the getters may read what it left
+  int        classes = 0;                   // of the last call: its classes (mixture), ...
+  int        chunks = 0, last_first = 0;    // ... its chunks, the first candidate of the last one
+  int        last_count = 0, last_keep = -1;
+  std::vector<int> last_slots;              // ... [candidate of the last chunk][3]: the matrix slots its record named
+  double     prof_ms = 0.0;                 // while profiling: its kernels (phyhip_profile_read_regraft, phyhip_profile_read_mixture_regraft)
+  int        prof_n = 0;
+  long long  prof_cand = 0;                 // ... and the candidates they served
+};
+
 struct SideUnits
 {
   struct
@@ -201,34 +221,12 @@ struct SideUnits
     int       prof_n = 0;
     long long prof_evals = 0;  // ... and the evaluations its searches took
   } brlen;
-  struct
-  { // phyhip_calculate_regraft_log_likelihoods
-    WorkSpace work;                          // kept vector, its exponents, then one chunk's matrices, tile sums, sums, lengths, records, flags
-    size_t    max_bytes = kRegraftWorkBytes; // the bound on it (phyhip_set_regraft_work_space)
-    bool      valid = false;                 // a call has completed: the getters may read what it left
-    int       chunks = 0, last_first = 0;    // of the last call: its chunks, the first candidate of the last one
-    int       last_count = 0, last_keep = -1;
-    std::vector<int> last_slots;             // ... [candidate of the last chunk][3]: the matrix slots its record named
-    double    prof_ms = 0.0;                 // while profiling: its kernels (phyhip_profile_read_regraft)
-    int       prof_n = 0;
-    long long prof_cand = 0;                 // ... and the candidates they served
-  } regraft;
-  struct
-  { // phyhip_calculate_mixture_regraft_log_likelihoods; all of it lives on the FIRST class instance (of each shard)
-    WorkSpace work;                          // kept vectors [class][P][S], their exponents, then one chunk's matrices, tile sums, sums, class table, records, lengths
-    size_t    max_bytes = kRegraftWorkBytes; // the bound on it (phyhip_set_mixture_regraft_work_space)
-    bool      valid = false;                 // a call has completed: the getters may read what it left
-    int       classes = 0;                   // of the last call: its classes, ...
-    int       chunks = 0, last_first = 0;    // ... its chunks, the first candidate of the last one
-    int       last_count = 0, last_keep = -1;
-    std::vector<int> last_slots;             // ... [candidate of the last chunk][3]: the matrix slots its record named
-    double    prof_ms = 0.0;                 // while profiling: its kernels (phyhip_profile_read_mixture_regraft)
-    int       prof_n = 0;
-    long long prof_cand = 0;                 // ... and the candidates they served
-  } mixregraft;
+  RegraftUnit regraft;    // phyhip_calculate_regraft_log_likelihoods (classes stays 0)
+  RegraftUnit mixregraft; // phyhip_calculate_mixture_regraft_log_likelihoods; all of it lives on the FIRST class instance (of each shard)
   struct
   { // phyhip_optimise_triples
-    WorkSpace work;                          // the three kept vectors, their exponents, then one chunk's matrices, products, exponents, records, results
+    WorkSpace work;                          // as `lay` places it
+    TripleLayout lay;                        // of the last call (phyhip_scan_plan.hpp)
     size_t    max_bytes = kRegraftWorkBytes; // the bound on it (phyhip_set_triple_work_space)
     bool      keep_valid = false;            // the last call kept a candidate that ran to its end: phyhip_get_triple_partials may read it
     double    prof_ms = 0.0;                 // while profiling: its kernel (phyhip_profile_read_triples)
@@ -241,6 +239,13 @@ inline SideUnits &side_of(Instance *I)
 {
   if (!I->side) I->side = new SideUnits;
   return *I->side;
+}
+
+// A side call has waited for the instance's stream and nothing queued is left: clean at once, as after a fenced evaluation
+// (phyhip_queue.hip) -- the Lk(b) / dLk calls that follow can be served resident again
+inline void side_stream_drained(Instance *I)
+{
+  I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch;
 }
 
 inline void side_release(Instance *I) // phyhip_finalize_instance

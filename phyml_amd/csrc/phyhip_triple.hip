@@ -35,6 +35,7 @@
 // Compiled with -disable-machine-licm, for brlen_opt_kernel's reason: hoisting the probe loop's invariants costs the registers
 // that the kept rounds are for.
 #include "phyhip_regraft_dev.hpp"
+#include "phyhip_scan.hpp" // the chunk walk; the work-space layout: phyhip_scan_plan.hpp
 #include "phyhip_brlen_step.h"
 
 namespace phyhip_host
@@ -412,20 +413,6 @@ __global__ __launch_bounds__(kTripleThreads<S>) void triple_kernel(const TripleP
   if (tid == 0) a.out[cand] = res;
 }
 
-// bytes of the work space one candidate of a chunk takes ...
-static size_t triple_exponent_ints(const Instance *I) { return ((size_t)I->P + 1) & ~(size_t)1; }
-static size_t triple_candidate_bytes(const Instance *I)
-{
-  return (3 * (size_t)I->C * I->S * I->S + (size_t)I->P * I->C * I->S) * sizeof(double) + triple_exponent_ints(I) * sizeof(int) +
-         sizeof(phyhip_triple_candidate) + sizeof(phyhip_triple_result);
-}
-// ... and of the three kept vectors with their exponents, which every call's layout reserves
-// (rounded up to 256 bytes: what lies behind them is read as double2)
-static size_t triple_keep_bytes(const Instance *I)
-{
-  return (3 * ((size_t)I->P * I->C * I->S * sizeof(double) + triple_exponent_ints(I) * sizeof(int)) + 255) & ~(size_t)255;
-}
-
 static int triple_run(Instance *I, const phyhip_triple_candidate *cand, int count, int iterMax, double tol, int keep, phyhip_triple_result *out)
 {
   static const char *const who = "phyhip_optimise_triples";
@@ -453,12 +440,10 @@ static int triple_run(Instance *I, const phyhip_triple_candidate *cand, int coun
   if ((rc = flush_sync(I))) return rc; // (queued matrix work and partial updates first: the path updates of the caller are seen)
   if ((rc = upload_masks(I))) return rc;
 
-  const size_t SS = (size_t)I->S * I->S, CS = (size_t)I->C * I->S, Pe = triple_exponent_ints(I);
-  const size_t per = triple_candidate_bytes(I), fixed = triple_keep_bytes(I);
-  size_t       chunk = U.max_bytes > fixed + per ? (U.max_bytes - fixed) / per : 1;
-  chunk = std::min(chunk, (size_t)count);
-  if ((rc = U.work.reserve(fixed + chunk * per, who))) return rc;
-  // layout: kept vectors | their exponents | matrices | products | exponents | records | results
+  const TripleLayout size(I->P, I->S, I->C, 0);
+  U.lay = TripleLayout(I->P, I->S, I->C, scan_chunk(U.max_bytes, size.fixed, size.per, count));
+  const TripleLayout &L = U.lay;
+  if ((rc = U.work.reserve(L.total, who))) return rc;
   TripleParams a;
   memset(&a, 0, sizeof a);
   DlkParams &q = a.q;
@@ -467,42 +452,34 @@ static int triple_run(Instance *I, const phyhip_triple_candidate *cand, int coun
   q.eval_dev = I->d_eval; q.rates_dev = I->d_catr; q.br_len_mult = I->br_len_mult; q.l_min = I->l_min; q.l_max = I->l_max;
   a.tip_codes = I->d_tipcodes; a.code_masks = I->d_masks; a.partials = I->d_partials; a.scales = I->d_scales;
   a.U = I->d_evec; a.V = I->d_ivec; a.R = I->d_eval;
-  a.Ppad = I->Ppad; a.Pe = (long long)Pe; a.tips = I->tips;
+  a.Ppad = I->Ppad; a.Pe = (long long)L.exp_ints; a.tips = I->tips;
   a.tol = tol; a.n_iter_max = iterMax; a.cap = brlen_trip_cap(I->l_min, I->l_max);
-  a.keep = (double *)U.work.ptr;
-  a.mats = (double *)((char *)U.work.ptr + fixed);
-  a.dot = a.mats + chunk * 3 * I->C * SS;
-  a.fact = (int *)(a.dot + chunk * (size_t)I->P * CS);
-  phyhip_triple_candidate *d_recs = (phyhip_triple_candidate *)(a.fact + chunk * Pe);
-  phyhip_triple_result    *d_out = (phyhip_triple_result *)(d_recs + chunk);
+  a.keep = U.work.at<double>(L.keep); a.mats = U.work.at<double>(L.mats); a.dot = U.work.at<double>(L.dot); a.fact = U.work.at<int>(L.fact);
+  phyhip_triple_candidate *d_recs = U.work.at<phyhip_triple_candidate>(L.recs);
+  phyhip_triple_result    *d_out = U.work.at<phyhip_triple_result>(L.out);
   a.recs = d_recs; a.out = d_out;
 
   const int layout = layout_of(I);
   SideTimer tm(I);
   long long evals = 0;
-  for (size_t first = 0; first < (size_t)count; first += chunk)
-  {
-    const size_t n = std::min(chunk, (size_t)count - first);
+  rc = for_each_chunk(count, L.chunk, keep, [&](size_t first, size_t n, int keep_cand) {
     HIPCHK(hipMemcpyAsync(d_recs, cand + first, n * sizeof *cand, hipMemcpyHostToDevice, I->stream));
     HIPCHK(hipMemsetAsync(d_out, 0xff, n * sizeof *d_out, I->stream)); // (a record nobody wrote reads as status -1 everywhere)
-    a.keep_cand = (keep >= (int)first && keep < (int)(first + n)) ? keep - (int)first : -1;
-    if ((rc = tm.tic())) return rc;
-    rc = dispatch_shape(I, [&](auto s, auto cp) {
-      constexpr int S_ = decltype(s)::value, CP_ = decltype(cp)::value;
-      if constexpr (CP_ <= 8)
-      {
-        constexpr int LS = S_ == 4 ? 2 : 1; // the instance's own layout of that state count (phyhip_layout.hpp)
-        if (layout == LS) hipLaunchKernelGGL((triple_kernel<S_, CP_, LS>), dim3((unsigned)n), dim3(kTripleThreads<S_>), 0, I->stream, a);
-        else if (layout == 0) hipLaunchKernelGGL((triple_kernel<S_, CP_, 0>), dim3((unsigned)n), dim3(kTripleThreads<S_>), 0, I->stream, a);
-        else return fail(PHYHIP_ERROR_GENERAL, "%s: buffer layout %d at %d states", who, layout, S_);
-      }
-      return 0;
+    a.keep_cand = keep_cand;
+    const int rt = side_timed(tm, I, U.prof_ms, [&] {
+      return dispatch_shape(I, [&](auto s, auto cp) {
+        constexpr int S_ = decltype(s)::value, CP_ = decltype(cp)::value;
+        if constexpr (CP_ <= 8)
+        {
+          constexpr int LS = S_ == 4 ? 2 : 1; // the instance's own layout of that state count (phyhip_layout.hpp)
+          if (layout == LS) hipLaunchKernelGGL((triple_kernel<S_, CP_, LS>), dim3((unsigned)n), dim3(kTripleThreads<S_>), 0, I->stream, a);
+          else if (layout == 0) hipLaunchKernelGGL((triple_kernel<S_, CP_, 0>), dim3((unsigned)n), dim3(kTripleThreads<S_>), 0, I->stream, a);
+          else return fail(PHYHIP_ERROR_GENERAL, "%s: buffer layout %d at %d states", who, layout, S_);
+        }
+        return 0;
+      });
     });
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if ((rc = tm.mark())) return rc;
-    HIPCHK(hipStreamSynchronize(I->stream));
-    if ((rc = tm.toc(U.prof_ms))) return rc;
+    if (rt) return rt;
     HIPCHK(hipMemcpy(out + first, d_out, n * sizeof *d_out, hipMemcpyDeviceToHost));
     for (size_t k = 0; k < n; ++k)
     {
@@ -510,16 +487,18 @@ static int triple_run(Instance *I, const phyhip_triple_candidate *cand, int coun
       if (r.status[0] < 0) return fail(PHYHIP_ERROR_GENERAL, "%s: candidate %zu finished without handing its result over", who, first + k);
       for (int i = 0; i < 3; ++i) evals += r.evaluations[i];
     }
-  }
+    return 0;
+  });
+  if (rc) return rc;
   U.keep_valid = keep >= 0 && out[keep].status[2] >= 0 && out[keep].status[2] < 3;
   if (I->prof)
   {
     ++U.prof_n;
     U.prof_evals += evals;
   }
-  // the stream has drained: clean at once -- the Lk(b) / dLk calls that follow can be served resident again; the flag the host reads
-  // (phyhip_get_numerical_warning) is the last candidate's last evaluation's
-  I->stream_dirty = false; I->clean_after = 0; ++I->clean_epoch;
+  // the Lk(b) / dLk calls that follow can be served resident again; the flag the host reads (phyhip_get_numerical_warning) is the
+  // last candidate's last evaluation's
+  side_stream_drained(I);
   *I->h_warn      = out[count - 1].warning;
   I->warn_current = true;
   return PHYHIP_SUCCESS;
@@ -554,11 +533,8 @@ int phyhip_get_triple_partials(int instance, int which, double *outPartials, int
   auto &U = side_of(I).triple;
   if (!U.keep_valid || !U.work.ptr)
     return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no phyhip_optimise_triples call before it that kept a candidate which ran to its end", who);
-  const size_t  PCS = (size_t)I->P * I->C * I->S, Pe = triple_exponent_ints(I);
-  const double *d_keep = (const double *)U.work.ptr;
-  if (outPartials) HIPCHK(hipMemcpy(outPartials, d_keep + (size_t)which * PCS, PCS * sizeof(double), hipMemcpyDeviceToHost));
-  if (outScaleFactors)
-    HIPCHK(hipMemcpy(outScaleFactors, reinterpret_cast<const int *>(d_keep + 3 * PCS) + (size_t)which * Pe, (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
+  if (outPartials) HIPCHK(hipMemcpy(outPartials, U.work.at<double>(U.lay.keep_of(which)), U.lay.vec_bytes, hipMemcpyDeviceToHost));
+  if (outScaleFactors) HIPCHK(hipMemcpy(outScaleFactors, U.work.at<int>(U.lay.exps_of(which)), (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
   return PHYHIP_SUCCESS;
 }
 

@@ -62,7 +62,7 @@ def test_the_bindings_and_the_constants():
     side = open(os.path.join(ROOT, "phyml_amd", "csrc", "phyhip_side.hpp")).read()
     assert "static_assert(sizeof(MixRegraftClass) == %d" % capi.MIXTURE_REGRAFT_CLASS_BYTES in src
     assert "static_assert(sizeof(MixRegraftHead) == %d" % capi.MIXTURE_REGRAFT_HEAD_BYTES in src
-    assert "} mixregraft;" in side and "&I->side->mixregraft.work" in side          # kept on the instance, released with it
+    assert "RegraftUnit mixregraft;" in side and "&I->side->mixregraft.work" in side          # kept on the instance, released with it
     # the work-space arithmetic of the header, as the bindings restate it
     assert capi.mixture_regraft_chunk_candidates(382, 4, 4) >= 512 and capi.mixture_regraft_chunk_candidates(429, 4, 20) >= 512
     K, P, S = 4, 300, 4
@@ -73,4 +73,6 @@ def test_the_bindings_and_the_constants():
     assert capi.mixture_regraft_chunk_candidates(P, K, S, 1) == 1
     # no floating-point atomics, no cooperative launch, no new environment switch in the unit
     for word in ("atomicAdd", "hipLaunchCooperativeKernel", "getenv(", "diag_env("):
+        for name in ("phyhip_scan_plan.hpp", "phyhip_scan.hpp"):
+            assert word not in open(os.path.join(ROOT, "phyml_amd", "csrc", name)).read(), (word, name)
         assert word not in src, word

@@ -74,7 +74,9 @@ def test_the_bindings_and_the_constants():
     assert callable(getattr(lktree.LkTree, "Regraft_Scan", None))
     src = open(os.path.join(ROOT, "phyml_amd", "csrc", "phyhip_regraft.hip")).read()
     side = open(os.path.join(ROOT, "phyml_amd", "csrc", "phyhip_side.hpp")).read()
-    assert int(re.search(r"constexpr int kRegraftTile = (\d+);", src).group(1)) == capi.REGRAFT_TILE
+    plan = open(os.path.join(ROOT, "phyml_amd", "csrc", "phyhip_scan_plan.hpp")).read()
+    driver = open(os.path.join(ROOT, "phyml_amd", "csrc", "phyhip_scan.hpp")).read()
+    assert int(re.search(r"constexpr int\s+kRegraftTile = (\d+);", plan).group(1)) == capi.REGRAFT_TILE
     assert int(re.search(r"constexpr int kRegraftMaxCategories = (\d+);", src).group(1)) == capi.REGRAFT_MAX_CATEGORIES
     assert "kRegraftWorkBytes = kDistBandBytes" in side and "kDistBandBytes = 128u << 20" in side and capi.REGRAFT_WORK_BYTES == 128 << 20
     assert capi.REGRAFT_SUBTREE_IS_LEFT == 1
@@ -87,7 +89,7 @@ def test_the_bindings_and_the_constants():
     assert capi.regraft_chunk_candidates(300, 4, 4, 1) == 1
     # no floating-point atomics, no cooperative launch, no new environment switch in the unit
     for word in ("atomicAdd", "hipLaunchCooperativeKernel", "getenv(", "diag_env("):
-        assert word not in src, word
+        assert word not in src and word not in plan and word not in driver, word
 
 
 def test_the_translation_unit_is_in_the_build_list():
