@@ -644,6 +644,36 @@ int phyhip_get_partial_parsimony(int instance, int bufferIndex, int *outUi, int 
    pattern x (operations + scored edges) since the previous read; reading resets all three.  Sharded: the slowest shard's time. */
 int phyhip_profile_read_parsimony(int instance, double *outKernelMs, int *outLaunches, double *outPatternUpdates);
 
+/* K regraft candidates of Spr_Pars in ONE call (src/spr.c:639-651 with spr_pars == YES: Graft_Subtree, Update_Partial_Pars(b_arrow,
+   n_link), Pars(b_arrow), Prune_Subtree for every target edge of a pruned subtree).  Candidate k, in the mode in use: J = the join of
+   child1 and child2 as Update_Partial_Pars forms it (src/pars.c:380-391, :359-375) -- never stored --, site[p] = Pars_Core of the edge
+   (J, subtree) (:411-433), outParsimony[k] = sum over patterns of site[p] * weight[p], exact in 64 bits.  Indices as above: below
+   tipCount a tip, else the plane of that buffer; child1 == child2 is allowed.
+   Unlike the six calls above, a scan is a call that puts work on the stream: it enters as the other candidate-list calls do (a
+   sharded instance's recorded calls drain, the large-grid resident workgroups leave).  Operations queued by
+   phyhip_update_partial_parsimony run first, in stream order (the path updates of Test_One_Spr_Target_Recur, src/spr.c:545), and
+   count as launches of phyhip_profile_read_parsimony like any other flush; the scan's own kernels do not.  Nothing else of the
+   instance changes but the call's work space (24 bytes a candidate and 8 per tile of 256 patterns, the kept plane and the kept site
+   scores) and its profile
+   counters: the planes, the site scores of the last scored edge and everything on the likelihood side stay.  A result depends on
+   the candidate alone -- not on count, its place in the list, the chunks (65535 candidates each) or the grid.  count == 0 succeeds.
+   keepCandidate (-1: none) keeps J and site[] of one candidate for the two getters below, whose shapes and mode rules are those of
+   phyhip_get_partial_parsimony; they return PHYHIP_ERROR_OUT_OF_RANGE before any scan, after a scan with -1, after a mode switch
+   through phyhip_set_parsimony, or for an array the mode does not hold.
+   Refused before any device work of any shard: what the parsimony calls refuse by kind of instance, and a call before
+   phyhip_set_parsimony; an index out of range, keepCandidate outside -1 .. count - 1, a NULL array with count > 0
+   (PHYHIP_ERROR_OUT_OF_RANGE); a pattern weight that is not an integer (PHYHIP_ERROR_NO_IMPLEMENTATION, as the edge call).
+   Sharded instances of one process: every shard scans its pattern range, the host adds the integer sums, the kept vectors are
+   concatenated.  Not built: mixture trees (MIXT_Pars). */
+typedef struct { int child1, child2, subtree; } phyhip_parsimony_candidate;
+int phyhip_calculate_regraft_parsimony(int instance, const phyhip_parsimony_candidate *candidates, int count, int keepCandidate,
+                                       long long *outParsimony /* [count] */);
+int phyhip_get_regraft_site_parsimony(int instance, int *outSitePars /* [pattern] */);
+int phyhip_get_regraft_partial_parsimony(int instance, int *outUi, int *outPars, int *outPPars /* [pattern][state] */);
+/* while phyhip_profile(instance, 1): milliseconds of the scan kernels, the calls and the candidates they served since the previous
+   read; reading resets all three.  Sharded: the time is added over the shards. */
+int phyhip_profile_read_regraft_parsimony(int instance, double *outKernelMs, int *outCalls, long long *outCandidates);
+
 /* ---- regraft scan (src/spr.c: Test_One_Spr_Target) ------------------------------------------------------------------------------ */
 
 /* K regraft candidates of one pruned subtree in ONE call.  Candidate k joins three vectors that exist already: outLogLikelihoods[k] is

@@ -320,6 +320,22 @@ void Get_Step_Mat(t_tree *tree);
 /* download hooks: the side of b at node d -- ui / pars [n_pattern] (Fitch) or p_pars [n_pattern][ns] (step matrix); NULL: not wanted */
 void Get_Partial_Pars(t_tree *tree, t_edge *b, t_node *d, int *ui, int *pars, int *p_pars);
 void Get_Site_Pars(t_tree *tree, int *site_pars);
+/* The parsimony regraft scan of one pruned subtree in ONE device call (phyhip_calculate_regraft_parsimony): what Test_One_Spr_Target
+   (src/spr.c:639-651) computes target by target under spr_pars == YES -- Update_Partial_Pars(b_arrow, n_link), Pars(b_arrow) -- for n
+   target edges at once.  The subtree is the vector of b_sub on d_sub's side (d_sub a tip: its tip vector); candidate i joins the two
+   side vectors of b_target[i] (the right one is the tip where rght->tax); buffer indices are resolved as Lk_Regraft_Scan resolves
+   them.  pars[i]: what Pars(b_arrow) would leave in tree->c_pars for candidate i.  keep (-1: none): the candidate whose joined
+   vector and per-pattern scores stay for Get_Regraft_Partial_Pars / Get_Regraft_Site_Pars (shapes as Get_Partial_Pars /
+   Get_Site_Pars).  Updates queued with Update_Partial_Pars before the call (the path updates of Test_One_Spr_Target_Recur,
+   src/spr.c:545) are seen.  tree->c_pars, tree->site_pars and every plane are left alone.  The call is always the scan: batching
+   is the caller's choice.  A sum above INT_MAX (the reference's c_pars is an int), a weight that is not a whole number or any
+   refusal of the device call (include/phyhip.h) runs the exit handler; the caller then takes the targets one by one.
+   This layer has no Prune_Subtree / Graft_Subtree: on an INTACT tree the vectors are whatever the tree holds -- the side vectors of a
+   target edge still contain the subtree, so the numbers are those of the call sequence, not of a legal SPR move; a caller that has
+   pruned (tests/test_gpu_pars_regraft.py drives the device call over the pruned topology) gets the search's candidates. */
+void Pars_Regraft_Scan(t_tree *tree, t_edge *b_sub, t_node *d_sub, int n, t_edge *const *b_target, int keep, int *pars);
+void Get_Regraft_Partial_Pars(t_tree *tree, int *ui, int *pars, int *p_pars);
+void Get_Regraft_Site_Pars(t_tree *tree, int *site_pars);
 
 void Set_Exit_Handler(void (*handler)(const char *msg));
 

@@ -33,6 +33,11 @@ class RegraftCandidate(C.Structure):
                 ("child1Length", C.c_double), ("child2Length", C.c_double), ("subtreeLength", C.c_double)]
 
 
+class ParsimonyCandidate(C.Structure):
+    """phyhip_parsimony_candidate"""
+    _fields_ = [("child1", C.c_int), ("child2", C.c_int), ("subtree", C.c_int)]
+
+
 class TripleCandidate(C.Structure):
     """phyhip_triple_candidate"""
     _fields_ = [("partials", C.c_int * 3), ("flags", C.c_int), ("length", C.c_double * 3)]
@@ -73,6 +78,8 @@ SYMBOLS = [
     "phyhip_set_support_site_log_likelihoods", "phyhip_calculate_sh_support", "phyhip_get_support_alias_table", "phyhip_profile_read_support",
     "phyhip_set_parsimony", "phyhip_update_partial_parsimony", "phyhip_calculate_edge_parsimony", "phyhip_get_site_parsimony",
     "phyhip_get_partial_parsimony", "phyhip_profile_read_parsimony",
+    "phyhip_calculate_regraft_parsimony", "phyhip_get_regraft_site_parsimony", "phyhip_get_regraft_partial_parsimony",
+    "phyhip_profile_read_regraft_parsimony",
     "phyhip_optimise_edge_length", "phyhip_profile_read_edge_length",
     "phyhip_calculate_regraft_log_likelihoods", "phyhip_get_regraft_partials", "phyhip_get_regraft_transition_matrix",
     "phyhip_set_regraft_work_space", "phyhip_profile_read_regraft",
@@ -87,6 +94,21 @@ UNIQUE_ID_BYTES = 128
 PARS_TILE = 256  # kParsTile of phyml_amd/csrc/phyhip_pars.hip: patterns per workgroup of the parsimony kernels
 PARS_STAGING = 4096  # kParsStaging: operations one parsimony launch takes (a longer queue is launched as it fills)
 MAX_PARS = 1000000000  # src/utilities.h
+PARS_REGRAFT_SLAB_FACTOR = 8  # kParsScanSlabFactor of phyml_amd/csrc/phyhip_scan_plan.hpp
+PARS_REGRAFT_CHUNK = 65535  # kScanGridCap: candidates of one launch of regraft_parsimony
+PARS_REGRAFT_LDS = {"fitch": 32, "general": 64}  # kParsScanFitchLds, kParsScanGeneralLds (the step-matrix kernel: plus S * S ints)
+
+
+def pars_regraft_slabs(count, P, compute_units, factor=PARS_REGRAFT_SLAB_FACTOR):
+    """(slabs, records per slab) of one launch of regraft_parsimony over `count` <= PARS_REGRAFT_CHUNK candidates, as ParsScanSlabs
+    (phyml_amd/csrc/phyhip_scan_plan.hpp) cuts it: enough slabs to give every compute unit `factor` workgroups, no more than
+    candidates; every slab but the last holds that many records.  compute_units: Instance.details.computeUnits."""
+    if count == 0:
+        return 0, 0
+    tiles = max(1, (P + PARS_TILE - 1) // PARS_TILE)
+    want = min(count, max(1, (factor * compute_units + tiles - 1) // tiles))
+    size = (count + want - 1) // want
+    return (count + size - 1) // size, size
 ERROR_UNINITIALIZED_INSTANCE, ERROR_OUT_OF_RANGE, ERROR_NO_IMPLEMENTATION = -4, -5, -7
 ERROR_FLOATING_POINT = -8
 REGRAFT_SUBTREE_IS_LEFT = 1  # PHYHIP_REGRAFT_SUBTREE_IS_LEFT
@@ -460,6 +482,42 @@ class Instance:
         ms = C.c_double(0); n = C.c_int(0); u = C.c_double(0)
         _chk(self.L.phyhip_profile_read_parsimony(self.id, C.byref(ms), C.byref(n), C.byref(u)))
         return ms.value, n.value, u.value
+
+    # -- parsimony regraft scan (src/spr.c: Test_One_Spr_Target under spr_pars)
+    def regraft_parsimony(self, candidates, keep=-1):
+        """phyhip_calculate_regraft_parsimony: candidates = iterable of (child1, child2, subtree), or a prebuilt ParsimonyCandidate
+        array; keep: the candidate whose joined vector and site scores stay for the two getters.  Returns the sums [K] (int64)."""
+        if isinstance(candidates, C.Array):
+            arr, n = candidates, len(candidates)
+        else:
+            a = np.ascontiguousarray(np.array(list(candidates), dtype=np.int32).reshape(-1, 3))
+            n = int(a.shape[0])
+            arr = (ParsimonyCandidate * max(1, n)).from_buffer_copy(a.tobytes() if n else bytes(12))
+        out = np.zeros(n, np.int64)
+        _chk(self.L.phyhip_calculate_regraft_parsimony(self.id, arr, n, int(keep), _ptr(out)))
+        return out
+
+    def regraft_site_parsimony(self):
+        """phyhip_get_regraft_site_parsimony: the kept candidate's per-pattern scores"""
+        out = np.zeros(self.P, np.int32)
+        _chk(self.L.phyhip_get_regraft_site_parsimony(self.id, _ptr(out)))
+        return out
+
+    def regraft_partial_parsimony(self, general=False):
+        """phyhip_get_regraft_partial_parsimony: (ui, pars) of the kept candidate's joined vector, or -- general -- p_pars [pattern][state]"""
+        if general:
+            pp = np.zeros((self.P, self.S), np.int32)
+            _chk(self.L.phyhip_get_regraft_partial_parsimony(self.id, None, None, _ptr(pp)))
+            return pp
+        ui = np.zeros(self.P, np.int32); pars = np.zeros(self.P, np.int32)
+        _chk(self.L.phyhip_get_regraft_partial_parsimony(self.id, _ptr(ui), _ptr(pars), None))
+        return ui, pars
+
+    def profile_read_regraft_parsimony(self):
+        """(kernel ms, calls, candidates) of the parsimony regraft scans since the previous read, while profile(1)"""
+        ms = C.c_double(0); n = C.c_int(0); nc = C.c_longlong(0)
+        _chk(self.L.phyhip_profile_read_regraft_parsimony(self.id, C.byref(ms), C.byref(n), C.byref(nc)))
+        return ms.value, n.value, nc.value
 
     def get_partials(self, buf):
         out = np.zeros((self.P, self.C * self.S))

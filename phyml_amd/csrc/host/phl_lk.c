@@ -12,6 +12,7 @@
 #include "../phyhip_brlen_step.h"
 
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1272,4 +1273,44 @@ void Get_Partial_Pars(t_tree *tree, t_edge *b, t_node *d, int *ui, int *pars, in
 void Get_Site_Pars(t_tree *tree, int *site_pars)
 {
   CHK(phyhip_get_site_parsimony(tree->b_inst, site_pars));
+}
+
+/* Test_One_Spr_Target (src/spr.c:639-651, spr_pars == YES) for n target edges in one device call; see include/phyhip_lk.h */
+void Pars_Regraft_Scan(t_tree *tree, t_edge *b_sub, t_node *d_sub, int n, t_edge *const *b_target, int keep, int *pars)
+{
+  if (n <= 0) return;
+  if (tree->e_root) { Lk_Exit("Pars_Regraft_Scan", "rooted trees are not built"); return; }
+  if (d_sub != b_sub->left && d_sub != b_sub->rght) { Lk_Exit("Pars_Regraft_Scan", "d_sub is not an end of b_sub"); return; }
+  phyhip_parsimony_candidate *c = (phyhip_parsimony_candidate *)calloc((size_t)n, sizeof *c);
+  long long *sum = (long long *)calloc((size_t)n, sizeof *sum);
+  if (!c || !sum) { free(c); free(sum); Lk_Exit("Pars_Regraft_Scan", "out of memory"); return; }
+  const int sub = d_sub->tax ? d_sub->num : (d_sub == b_sub->left ? b_sub->p_lk_left_idx : b_sub->p_lk_rght_idx);
+  for (int i = 0; i < n; ++i)
+  {
+    const t_edge *b = b_target[i];
+    c[i].child1  = b->left->tax ? b->left->num : b->p_lk_left_idx; /* as Pars_Score resolves the two sides */
+    c[i].child2  = b->rght->tax ? b->p_lk_tip_idx : b->p_lk_rght_idx;
+    c[i].subtree = sub;
+  }
+  const int rc = phyhip_calculate_regraft_parsimony(tree->b_inst, c, n, keep, sum);
+  int over = -1;
+  for (int i = 0; rc >= 0 && i < n; ++i)
+  {
+    if (sum[i] > INT_MAX && over < 0) over = i;
+    pars[i] = (int)sum[i];
+  }
+  free(c);
+  free(sum);
+  if (rc < 0) Lk_Exit("phyhip_calculate_regraft_parsimony", phyhip_get_last_error());
+  else if (over >= 0) Lk_Exit("Pars_Regraft_Scan", "a candidate's parsimony does not fit the reference's int");
+}
+
+void Get_Regraft_Partial_Pars(t_tree *tree, int *ui, int *pars, int *p_pars)
+{
+  CHK(phyhip_get_regraft_partial_parsimony(tree->b_inst, ui, pars, p_pars));
+}
+
+void Get_Regraft_Site_Pars(t_tree *tree, int *site_pars)
+{
+  CHK(phyhip_get_regraft_site_parsimony(tree->b_inst, site_pars));
 }

@@ -23,9 +23,12 @@
 // The weighted sum is a 64-bit integer: per lane, wave shuffle, one atomic add per wave into a zeroed word -- integer adds commute,
 // the result is the same for any grid.  Weights that are not integers are refused (the reference truncates a double into an int at
 // every pattern, which is order-dependent: the host layer runs that loop over the downloaded site_pars).
+// phyhip_calculate_regraft_parsimony, phyhip_get_regraft_site_parsimony, phyhip_get_regraft_partial_parsimony and
+// phyhip_profile_read_regraft_parsimony: K regraft candidates of Spr_Pars in one call (the kernels and their comment: below the step
+// matrix; the host driver: phyhip_scan.hpp).
 // The queue of this unit is its own: no call here flushes a queued likelihood operation or writes partials, scale vectors,
 // matrices, site outputs or the warning flag, and none is a step of the call sequence the resident evaluators watch.
-#include "phyhip_side.hpp"
+#include "phyhip_scan.hpp"
 #include "phyhip_layout.hpp"
 
 namespace phyhip_host
@@ -71,6 +74,17 @@ struct ParsState
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pairs;
   double     prof_ms = 0.0, prof_updates = 0.0;
   int        prof_n = 0;
+  struct
+  { // phyhip_calculate_regraft_parsimony
+    WorkSpace      work;               // as `lay` places it
+    ParsScanLayout lay;                // of the last call (phyhip_scan_plan.hpp): the getters read through it
+    bool           keep_valid = false; // the last call kept a candidate: the two getters may read it
+    std::vector<ParsScanRec>        recs;
+    std::vector<unsigned long long> down;
+    double         prof_ms = 0.0;      // while profiling: its kernels (phyhip_profile_read_regraft_parsimony)
+    int            prof_n = 0;
+    long long      prof_cand = 0;      // ... and the candidates they served
+  } scan;
 };
 
 // ---- Fitch -------------------------------------------------------------------------------------------------------------------------
@@ -219,6 +233,197 @@ template <int S> __global__ __launch_bounds__(kParsTile) void pars_general_kerne
   if (q.score && q.w) pars_add_sum(q, acc);
 }
 
+// ---- regraft scan ------------------------------------------------------------------------------------------------------------------
+// phyhip_calculate_regraft_parsimony: candidate k is J = the join of (child1, child2) -- an Update_Partial_Pars that stores nothing
+// -- and the score of the edge (J, subtree).  Grid: x = pattern tiles, y = slabs of the launch's candidates; a workgroup walks its
+// slab's records (wave-uniform addresses), the next record's operands loaded before this candidate is reduced.  Bit 0 of a record's
+// flags: its subtree is the previous record's (never set on a slab's first record), the operand stays in registers.  A candidate's
+// weighted sum: per lane, wave shuffle, the waves of the workgroup through LDS, then ONE 64-bit store per workgroup -- its partial
+// of (candidate, tile) -- and pars_regraft_sum adds a candidate's partials with one wave: integers, the same for any grid.  (One
+// atomic add per workgroup into the candidate's word was measured first: at 100 000 patterns the 391 adds per word, eight words a
+// cache line, bound the kernel -- 42.7 against 10.2 us at 8 candidates; profiles/parsimony_regraft_scan.md.)  The kept candidate's
+// J and site scores are stored by the workgroups of its slab, every lane its own patterns.
+
+struct ParsScanParams
+{
+  ParsParams          q;     // (ops, site, sum, n_ops, score, b1, b2 unused; w: the integer weights, zero behind P)
+  const ParsScanRec  *recs;  // [n]
+  unsigned long long *sums;  // [n]: written by pars_regraft_sum
+  int2               *keep_fitch; // [Pp]
+  int                *keep_gen;   // [S][Pp]
+  int                *keep_site;  // [Pp]
+  int                 n, slab, keep_cand;
+  unsigned long long *tile_sums; // [n][tiles]
+  int                 tiles;
+};
+
+constexpr int kParsScanFitchWaves = kParsTile / 2 / 64, kParsScanGeneralWaves = kParsTile / 64;
+constexpr int kParsScanFitchLds = 2 * kParsScanFitchWaves * (int)sizeof(long long);     // capi.py: PARS_REGRAFT_LDS
+constexpr int kParsScanGeneralLds = 2 * kParsScanGeneralWaves * (int)sizeof(long long); // ... plus S * S ints
+
+// candidate k's sum over the workgroup; ws[k & 1]: two sets of slots, so that one barrier per candidate is enough (a slot written for
+// candidate k is read before the barrier of k + 1 and written again behind it)
+template <int NW> __device__ __forceinline__ void pars_scan_sum(long long acc, long long (*ws)[NW], int k, const ParsScanParams &a)
+{
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) ws[k & 1][threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    long long s = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) s += ws[k & 1][w];
+    a.tile_sums[(size_t)k * a.tiles + blockIdx.x] = (unsigned long long)s;
+  }
+}
+
+// a candidate's tile sums added by one wave
+__global__ __launch_bounds__(64) void pars_regraft_sum(const unsigned long long *__restrict__ tile_sums, unsigned long long *__restrict__ out, const int tiles)
+{
+  const unsigned long long *row = tile_sums + (size_t)blockIdx.x * tiles;
+  unsigned long long s = 0;
+  for (int t = threadIdx.x; t < tiles; t += 64) s += row[t];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+template <int S> __global__ __launch_bounds__(kParsTile / 2) void pars_regraft_fitch(const ParsScanParams a)
+{
+  __shared__ long long ws[2][kParsScanFitchWaves];
+  const ParsParams &q = a.q;
+  const long long p = ((long long)blockIdx.x * (kParsTile / 2) + threadIdx.x) * 2; // (p + 1 < Pp: Pp is even)
+  const bool      in = p < q.P, two = p + 1 < q.P;
+  const int       first = (int)blockIdx.y * a.slab, last = first + a.slab < a.n ? first + a.slab : a.n;
+  const int4      zero = make_int4(0, 0, 0, 0);
+  long long       w0 = 0, w1 = 0;
+  int4            c1 = zero, c2 = zero, sub = zero;
+  if (in)
+  {
+    const ParsScanRec r = a.recs[first];
+    w0 = q.w[p];
+    w1 = two ? q.w[p + 1] : 0ll;
+    c1 = fitch_load<S>(q, r.c1, p, two);
+    c2 = fitch_load<S>(q, r.c2, p, two);
+    sub = fitch_load<S>(q, r.sub, p, two);
+  }
+  for (int k = first; k < last; ++k)
+  {
+    int4 n1 = zero, n2 = zero, ns = sub;
+    if (k + 1 < last && in)
+    { // the next candidate's operands, before this one is reduced
+      const ParsScanRec nr = a.recs[k + 1];
+      n1 = fitch_load<S>(q, nr.c1, p, two);
+      n2 = fitch_load<S>(q, nr.c2, p, two);
+      if (!(nr.flags & 1)) ns = fitch_load<S>(q, nr.sub, p, two);
+    }
+    const int4 j = fitch_join(c1, c2);
+    const int  s0 = j.y + sub.y + ((j.x & sub.x) ? 0 : 1), s1 = j.w + sub.w + ((j.z & sub.z) ? 0 : 1); // src/pars.c:432-433
+    if (k == a.keep_cand && in)
+    {
+      *reinterpret_cast<int4 *>(a.keep_fitch + p) = j;
+      a.keep_site[p] = s0;
+      if (two) a.keep_site[p + 1] = s1;
+    }
+    pars_scan_sum<kParsScanFitchWaves>((long long)s0 * w0 + (long long)s1 * w1, ws, k, a);
+    c1 = n1; c2 = n2; sub = ns;
+  }
+}
+
+// One row of the min-plus product: min(MAX_PARS, min_j(v[j] + step[i][j])) (src/pars.c:359-375, :411-427); row i of the matrix from
+// LDS at a wave-uniform address
+template <int S> __device__ __forceinline__ int general_row_min(const int *step, int i, const int (&v)[S])
+{
+  int x = kMaxPars;
+#pragma unroll
+  for (int j = 0; j < S; ++j)
+  {
+    const int t = v[j] + step[i * S + j];
+    x = t < x ? t : x;
+  }
+  return x;
+}
+
+// general_load for the scan: the plane's S rows at wave-uniform 64-bit bases plus ONE 32-bit byte offset of the lane (a pattern count
+// above 2^30 is refused by the host), so that a load in flight holds no address registers of its own
+template <int S> __device__ __forceinline__ void scan_general_load(const ParsParams &q, int b, long long p, unsigned lane_bytes, int (&v)[S])
+{
+  if (b < q.tips)
+  {
+    const uint32_t mask = tip_state_mask<S>(q.tip_codes, q.code_masks, q.Ppad, b, p);
+#pragma unroll
+    for (int j = 0; j < S; ++j) v[j] = ((mask >> j) & 1u) ? 0 : kMaxPars;
+  }
+  else
+  {
+    const char *plane = reinterpret_cast<const char *>(q.gen + (size_t)(b - q.tips) * S * q.Pp);
+#pragma unroll
+    for (int j = 0; j < S; ++j) v[j] = *reinterpret_cast<const int *>(plane + (size_t)j * q.Pp * sizeof(int) + lane_bytes);
+  }
+}
+
+// Registers of a lane: the subtree's S minima, the two children (2 S), J (S).  The children are dead once J is formed: the next
+// record's are loaded into their registers in front of the third min-plus product, which hides them.  The loops over i stay loops at
+// 20 states, as in general_step (unrolled, the matrix entries are hoisted and spill: tried, 243 spilled registers even with the rows
+// fenced off from each other).  general_step's rows go to memory as they are formed; these stay in registers, so J[i] and min_r[i]
+// are registers chosen by a wave-uniform index (the index mode, no scratch), and an array indexed that way is a register tuple of
+// the next power of two: 32 registers for 20 values.
+template <int S> __global__ __launch_bounds__(kParsTile) void pars_regraft_general(const ParsScanParams a)
+{
+  __shared__ int       step[S * S];
+  __shared__ long long ws[2][kParsScanGeneralWaves];
+  const ParsParams &q = a.q;
+  for (int i = threadIdx.x; i < S * S; i += kParsTile) step[i] = q.step[i];
+  __syncthreads();
+  const long long p = (long long)blockIdx.x * kParsTile + threadIdx.x;
+  const bool      in = p < q.P;
+  const long long pl = in ? p : 0; // a lane behind the last pattern reads pattern 0 and weighs it 0: no load below is conditional
+  const unsigned  lane_bytes = (unsigned)pl * (unsigned)sizeof(int);
+  const int       first = (int)blockIdx.y * a.slab, last = first + a.slab < a.n ? first + a.slab : a.n;
+  const long long w = in ? q.w[p] : 0ll;
+  constexpr int   kRows = S <= 4 ? S : 1;
+  int v1[S], v2[S], min_r[S], J[S];
+  {
+    const ParsScanRec r = a.recs[first];
+    scan_general_load<S>(q, r.sub, pl, lane_bytes, J);
+#pragma unroll kRows
+    for (int i = 0; i < S; ++i) min_r[i] = general_row_min<S>(step, i, J); // once per subtree, shared by the candidates that follow
+    scan_general_load<S>(q, r.c1, pl, lane_bytes, v1);
+    scan_general_load<S>(q, r.c2, pl, lane_bytes, v2);
+  }
+  for (int k = first; k < last; ++k)
+  {
+#pragma unroll kRows
+    for (int i = 0; i < S; ++i) J[i] = general_row_min<S>(step, i, v1) + general_row_min<S>(step, i, v2);
+    // the next candidate's children, before this one is scored and reduced (behind the slab's last record: its own once more)
+    const ParsScanRec nr = a.recs[k + 1 < last ? k + 1 : k];
+    scan_general_load<S>(q, nr.c1, pl, lane_bytes, v1);
+    scan_general_load<S>(q, nr.c2, pl, lane_bytes, v2);
+    const bool new_sub = k + 1 < last && !(nr.flags & 1);
+    if (k == a.keep_cand && in)
+    {
+#pragma unroll
+      for (int i = 0; i < S; ++i) a.keep_gen[(size_t)i * q.Pp + p] = J[i];
+    }
+    int site = kMaxPars;
+#pragma unroll kRows
+    for (int i = 0; i < S; ++i)
+    {
+      const int t = general_row_min<S>(step, i, J) + min_r[i];
+      site = t < site ? t : site;
+    }
+    if (k == a.keep_cand && in) a.keep_site[p] = site;
+    pars_scan_sum<kParsScanGeneralWaves>((long long)site * w, ws, k, a);
+    if (new_sub)
+    { // (wave-uniform: the record is)
+      scan_general_load<S>(q, nr.sub, pl, lane_bytes, J);
+#pragma unroll kRows
+      for (int i = 0; i < S; ++i) min_r[i] = general_row_min<S>(step, i, J);
+    }
+  }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 
 static void pars_free_planes(ParsState *T)
@@ -235,6 +440,7 @@ void pars_release(Instance *I)
   ParsState *T = I->pars;
   if (!T) return;
   pars_free_planes(T);
+  T->scan.work.release();
   void *dev[] = {T->d_site, T->d_w, T->d_sum, T->d_ops[0], T->d_ops[1]};
   for (void *x : dev)
     if (x) (void)hipFree(x);
@@ -374,6 +580,7 @@ static int pars_set(Instance *I, int general, const int *step)
     pars_free_planes(T);
     T->general = -1;
     T->scored = false;
+    T->scan.keep_valid = false; // (the kept plane of a regraft scan has the other mode's shape)
     if (mode == 0)
     {
       if ((rc = side_alloc((void **)&T->d_fitch, nin * Pp * sizeof(int2), who))) return rc;
@@ -505,6 +712,133 @@ static int pars_get_partial(Instance *I, int buf, int *ui, int *pars, int *ppars
   return PHYHIP_SUCCESS;
 }
 
+// ---- regraft scan: host side -------------------------------------------------------------------------------------------------------
+
+static const char *const kParsScan = "phyhip_calculate_regraft_parsimony";
+
+// every check of a scan, before any device work of any shard
+static int pars_scan_check(Instance *I, const phyhip_parsimony_candidate *cand, int count)
+{
+  int rc;
+  if ((rc = pars_gate(I, kParsScan, true))) return rc;
+  if (I->P > (1ll << 30)) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: not built for more than 2^30 patterns (%lld)", kParsScan, I->P);
+  for (int k = 0; k < count; ++k)
+    if ((rc = check_partial_index(I, cand[k].child1, true)) || (rc = check_partial_index(I, cand[k].child2, true)) ||
+        (rc = check_partial_index(I, cand[k].subtree, true)))
+      return fail(rc, "%s: candidate %d: %s", kParsScan, k, std::string(g_err).c_str());
+  if (count == 0) return 0;
+  if ((rc = pars_weights(I))) return rc;
+  if (!I->pars->w_integer)
+    return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "%s: a pattern weight is not an integer (score the candidates edge by edge and add site_pars * wght on the host)", kParsScan);
+  return 0;
+}
+
+// what is queued, then the candidates in chunks: one copy up, the scan kernel and the sum kernel, one wait and one copy down each;
+// sums[k]: this shard's
+static int pars_scan_run(Instance *I, const phyhip_parsimony_candidate *cand, int count, int keep, long long *sums)
+{
+  ParsState *T = I->pars;
+  auto      &U = T->scan;
+  int        rc;
+  U.keep_valid = false;
+  if (count == 0) return 0;
+  if ((rc = pars_launch(I, false, 0, 0, false))) return rc; // (the path updates of the caller, in stream order)
+  if (I->S > 8 && (rc = upload_masks(I))) return rc;
+  U.lay = ParsScanLayout((size_t)I->P, (size_t)I->S, T->general != 0, std::min((size_t)count, kScanGridCap));
+  const ParsScanLayout &L = U.lay;
+  if ((rc = U.work.reserve(L.total, kParsScan))) return rc;
+  ParsScanParams a;
+  memset(&a, 0, sizeof a);
+  a.q.tip_codes = I->d_tipcodes; a.q.code_masks = I->d_masks; a.q.fitch = T->d_fitch; a.q.gen = T->d_gen; a.q.step = T->d_step;
+  a.q.w = T->d_w; a.q.P = I->P; a.q.Pp = T->Pp; a.q.Ppad = I->Ppad; a.q.tips = I->tips;
+  ParsScanRec *const d_recs = U.work.at<ParsScanRec>(L.recs);
+  a.recs = d_recs; a.sums = U.work.at<unsigned long long>(L.sums);
+  a.keep_fitch = U.work.at<int2>(L.keep); a.keep_gen = U.work.at<int>(L.keep); a.keep_site = U.work.at<int>(L.site);
+  const size_t tiles = (size_t)((I->P + kParsTile - 1) / kParsTile);
+  a.tile_sums = U.work.at<unsigned long long>(L.tile_sums); a.tiles = (int)tiles;
+  SideTimer    tm(I);
+  rc = for_each_chunk(count, L.chunk, keep, [&](size_t first, size_t n, int keep_cand) {
+    const ParsScanSlabs slabs(n, tiles, (size_t)(I->cus > 0 ? I->cus : 256));
+    U.recs.resize(n);
+    for (size_t k = 0; k < n; ++k)
+    {
+      const phyhip_parsimony_candidate &c = cand[first + k];
+      U.recs[k] = ParsScanRec{c.child1, c.child2, c.subtree, (k % slabs.size != 0 && c.subtree == cand[first + k - 1].subtree) ? 1 : 0};
+    }
+    HIPCHK(hipMemcpyAsync(d_recs, U.recs.data(), n * sizeof(ParsScanRec), hipMemcpyHostToDevice, I->stream));
+    a.n = (int)n; a.slab = (int)slabs.size; a.keep_cand = keep_cand;
+    const dim3 grid((unsigned)tiles, (unsigned)slabs.count);
+    const int  rt = side_timed(tm, I, U.prof_ms, [&] {
+      if (!T->general)
+      {
+        if (I->S == 4) hipLaunchKernelGGL(pars_regraft_fitch<4>, grid, dim3(kParsTile / 2), 0, I->stream, a);
+        else hipLaunchKernelGGL(pars_regraft_fitch<20>, grid, dim3(kParsTile / 2), 0, I->stream, a);
+      }
+      else
+      {
+        if (I->S == 4) hipLaunchKernelGGL(pars_regraft_general<4>, grid, dim3(kParsTile), 0, I->stream, a);
+        else hipLaunchKernelGGL(pars_regraft_general<20>, grid, dim3(kParsTile), 0, I->stream, a);
+      }
+      hipLaunchKernelGGL(pars_regraft_sum, dim3((unsigned)n), dim3(64), 0, I->stream, a.tile_sums, a.sums, a.tiles);
+      return 0;
+    });
+    if (rt) return rt;
+    U.down.resize(n);
+    HIPCHK(hipMemcpy(U.down.data(), a.sums, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n; ++k) sums[first + k] = (long long)U.down[k];
+    return 0;
+  });
+  if (rc) return rc;
+  U.keep_valid = keep >= 0;
+  if (I->prof) ++U.prof_n, U.prof_cand += count;
+  return 0;
+}
+
+static int pars_scan_kept(Instance *I, const char *who)
+{
+  if (const int rc = pars_gate(I, who, true)) return rc;
+  const auto &U = I->pars->scan;
+  if (!U.keep_valid || !U.work.ptr) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: no %s call before it that kept a candidate", who, kParsScan);
+  return 0;
+}
+
+static int pars_scan_get_site(Instance *I, int *out)
+{
+  if (const int rc = pars_scan_kept(I, "phyhip_get_regraft_site_parsimony")) return rc;
+  const auto &U = I->pars->scan;
+  HIPCHK(hipMemcpy(out, U.work.at<int>(U.lay.site), (size_t)I->P * sizeof(int), hipMemcpyDeviceToHost));
+  return PHYHIP_SUCCESS;
+}
+
+static int pars_scan_get_partial(Instance *I, int *ui, int *pars, int *ppars)
+{
+  static const char *const who = "phyhip_get_regraft_partial_parsimony";
+  if (const int rc = pars_scan_kept(I, who)) return rc;
+  ParsState *T = I->pars;
+  if (T->general ? (ui || pars) : (ppars != nullptr))
+    return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: %s", who, T->general ? "the step-matrix mode holds no ui / pars" : "the Fitch mode holds no p_pars");
+  const auto  &U = T->scan;
+  const size_t P = (size_t)I->P, Pp = U.lay.Pp, S = (size_t)I->S;
+  if (!T->general)
+  {
+    std::vector<int2> h(Pp);
+    HIPCHK(hipMemcpy(h.data(), U.work.at<int2>(U.lay.keep), Pp * sizeof(int2), hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < P; ++p)
+    {
+      if (ui) ui[p] = h[p].x;
+      if (pars) pars[p] = h[p].y;
+    }
+  }
+  else if (ppars)
+  {
+    std::vector<int> h(S * Pp);
+    HIPCHK(hipMemcpy(h.data(), U.work.at<int>(U.lay.keep), S * Pp * sizeof(int), hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < P; ++p)
+      for (size_t s = 0; s < S; ++s) ppars[p * S + s] = h[s * Pp + p];
+  }
+  return PHYHIP_SUCCESS;
+}
+
 static int pars_profile_gate(Instance *I, double *ms, int *n, double *up)
 {
   int rc;
@@ -575,6 +909,65 @@ int phyhip_profile_read_parsimony(int instance, double *outKernelMs, int *outLau
   if (outKernelMs) *outKernelMs = ms;
   if (outLaunches) *outLaunches = n;
   if (outPatternUpdates) *outPatternUpdates = up;
+  return PHYHIP_SUCCESS;
+}
+
+// A scan, unlike the six calls above, is a call that puts work on the stream: it enters as the other candidate-list calls do (the
+// group drained, the large-grid resident workgroups leave), every shard checked before any shard runs.
+
+int phyhip_calculate_regraft_parsimony(int instance, const phyhip_parsimony_candidate *candidates, int count, int keepCandidate, long long *outParsimony)
+{
+  if (count < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: candidate count %d", kParsScan, count);
+  if (count > 0 && (!candidates || !outParsimony)) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: a NULL array for %d candidates", kParsScan, count);
+  if (keepCandidate < -1 || keepCandidate >= count) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "%s: keepCandidate %d of %d candidates", kParsScan, keepCandidate, count);
+  SideShards s;
+  int rc = side_collect(instance, kParsScan, kRefuseRank | kRefuseClassAxis | kRefuseStates, s);
+  if (rc < 0) return rc;
+  for (Instance *I : s.sh)
+    if ((rc = pars_scan_check(I, candidates, count))) return rc;
+  std::vector<long long> part((size_t)count), sum((size_t)count, 0ll);
+  for (Instance *I : s.sh)
+  { // every shard scans its pattern range; the integer sums are added
+    if ((rc = pars_scan_run(I, candidates, count, keepCandidate, part.data()))) return rc;
+    for (size_t k = 0; k < sum.size(); ++k) sum[k] += part[k];
+  }
+  std::copy(sum.begin(), sum.end(), outParsimony);
+  return PHYHIP_SUCCESS;
+}
+
+int phyhip_get_regraft_site_parsimony(int instance, int *outSitePars)
+{
+  if (!outSitePars) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "phyhip_get_regraft_site_parsimony: a NULL array");
+  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long lo, long long) { return pars_scan_get_site(I, outSitePars + lo); });
+}
+
+int phyhip_get_regraft_partial_parsimony(int instance, int *outUi, int *outPars, int *outPPars)
+{
+  return side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long lo, long long) {
+    return pars_scan_get_partial(I, outUi ? outUi + lo : nullptr, outPars ? outPars + lo : nullptr, outPPars ? outPPars + lo * I->S : nullptr);
+  });
+}
+
+// read and reset: the time is added over the shards; calls and candidates are the same on every shard, the first one's are taken
+int phyhip_profile_read_regraft_parsimony(int instance, double *outKernelMs, int *outCalls, long long *outCandidates)
+{
+  double    ms = 0.0;
+  int       n = 0;
+  long long nc = 0;
+  bool      first = true;
+  const int rc = side_each<kSideDrain, kSideCall>(instance, [&](Instance *I, long long, long long) {
+    if (const int r = pars_gate(I, "phyhip_profile_read_regraft_parsimony", true)) return r;
+    auto &U = I->pars->scan;
+    ms += U.prof_ms;
+    if (first) n = U.prof_n, nc = U.prof_cand;
+    first = false;
+    U.prof_ms = 0.0; U.prof_n = 0; U.prof_cand = 0;
+    return 0;
+  });
+  if (rc < 0) return rc;
+  if (outKernelMs) *outKernelMs = ms;
+  if (outCalls) *outCalls = n;
+  if (outCandidates) *outCandidates = nc;
   return PHYHIP_SUCCESS;
 }
 

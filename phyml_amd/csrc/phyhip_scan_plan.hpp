@@ -1,5 +1,6 @@
 // phyhip_scan_plan.hpp -- the planning of the calls that take a list of K candidates and run it in chunks under a work-space bound
-// (phyhip_regraft.hip: the plain and the mixture regraft scan; phyhip_triple.hip: Triple_Dist): how many candidates a chunk holds,
+// (phyhip_regraft.hip: the plain and the mixture regraft scan; phyhip_triple.hip: Triple_Dist; phyhip_pars.hip: the parsimony
+// regraft scan, whose chunks are bounded by the grid alone): how many candidates a chunk holds,
 // where every region of the work space lies, which matrix slot a length of the chunk gets, and the record a scan kernel reads.
 // The ONE statement of those layouts: the runs place their device pointers with it, the getters read through the layout the run
 // left on the unit (phyhip_side.hpp), and capi.*_chunk_candidates restates its sizes (tests/test_scan_plan.py holds the two equal).
@@ -99,6 +100,49 @@ struct TripleLayout
   }
   size_t keep_of(size_t which) const { return keep + which * vec_bytes; }
   size_t exps_of(size_t which) const { return exps + which * exp_ints * sizeof(int); }
+};
+
+// The work space of phyhip_calculate_regraft_parsimony, byte offsets:
+//   kept plane (Fitch: int2 [Pp]; step matrix: int [S][Pp]) | kept site scores int [Pp] | records | sums | tile sums
+// Pp: the pattern count rounded up to even, as the planes of phyhip_pars.hip.  A candidate costs its 16-byte record, its 8-byte
+// sum and 8 bytes per tile of 256 patterns (3 KB at 100 000 patterns), so the only bound on a chunk is the cap.
+#ifndef PHYHIP_PARS_SLAB_FACTOR
+#define PHYHIP_PARS_SLAB_FACTOR 8 // (measured against 4 and 16 with builds that define it otherwise: profiles/parsimony_regraft_scan.md)
+#endif
+constexpr int kParsScanSlabFactor = PHYHIP_PARS_SLAB_FACTOR; // slabs of a launch: enough for this many workgroups per compute unit (phyhip_pars.hip)
+struct ParsScanRec
+{
+  int c1, c2, sub, flags; // plane or tip index of the two children and the subtree; bit 0: the subtree of the slab's previous record
+};
+struct ParsScanLayout
+{
+  size_t chunk = 0, Pp = 0, plane_bytes = 0, site_bytes = 0;
+  size_t keep = 0, site = 0, recs = 0, sums = 0, tile_sums = 0, total = 0;
+  ParsScanLayout(size_t P = 0, size_t S = 0, bool general = false, size_t chunk_ = 0) : chunk(chunk_)
+  {
+    Pp = (P + 1) & ~(size_t)1;
+    plane_bytes = general ? S * Pp * sizeof(int) : Pp * 2 * sizeof(int);
+    site_bytes = Pp * sizeof(int);
+    site = keep + plane_bytes;
+    recs = (site + site_bytes + 15) & ~(size_t)15;
+    sums = recs + chunk * sizeof(ParsScanRec);
+    tile_sums = sums + chunk * sizeof(unsigned long long);
+    total = tile_sums + chunk * ((P + kRegraftTile - 1) / kRegraftTile) * sizeof(unsigned long long);
+  }
+};
+
+// how a launch of n candidates over `tiles` pattern tiles is cut into slabs (the grid's second dimension): as many slabs as give
+// every compute unit kParsScanSlabFactor workgroups, no more than candidates; every slab but the last holds `size` records
+struct ParsScanSlabs
+{
+  size_t count = 0, size = 0;
+  ParsScanSlabs(size_t n, size_t tiles, size_t compute_units, size_t factor = kParsScanSlabFactor)
+  {
+    if (n == 0) return;
+    const size_t want = std::min(n, std::max<size_t>(1, (factor * compute_units + tiles - 1) / std::max<size_t>(1, tiles)));
+    size = (n + want - 1) / want;
+    count = (n + size - 1) / size;
+  }
 };
 
 // a length's 64 bits -> its matrix slot, in first-seen order: identical lengths of a chunk are built once (+0.0 and -0.0, or two

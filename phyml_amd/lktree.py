@@ -305,6 +305,33 @@ class LkTree:
         self.L.Get_Partial_Pars(self.tree, self.edge(b), d, ip(ui), ip(pars), None); _raise_if_error()
         return ui, pars
 
+    def Pars_Regraft_Scan(self, b_sub, d_sub, targets, keep=-1):
+        """Pars_Regraft_Scan: the parsimony scores [n] of regrafting the subtree of edge b_sub on node d_sub's side onto each edge of
+        `targets` -- one device call.  keep: the candidate whose vectors stay for Get_Regraft_Partial_Pars / Get_Regraft_Site_Pars.
+        On an intact tree the vectors are whatever the tree holds (include/phyhip_lk.h)."""
+        n = len(targets)
+        tg = (C.POINTER(t_edge) * max(1, n))(*[self.edge(int(b)) for b in targets])
+        out = np.zeros(n, np.int32)
+        self.L.Pars_Regraft_Scan(self.tree, self.edge(int(b_sub)), self.node(int(d_sub)), n, tg, int(keep), out.ctypes.data_as(C.c_void_p))
+        _raise_if_error()
+        return out
+
+    def Get_Regraft_Partial_Pars(self):
+        """(ui, pars) of the kept candidate's joined vector, or p_pars [pattern][state] in the step-matrix mode"""
+        ip = lambda a: a.ctypes.data_as(C.c_void_p)
+        if self.tree.contents.general_pars:
+            pp = np.zeros((self.P, self.S), np.int32)
+            self.L.Get_Regraft_Partial_Pars(self.tree, None, None, ip(pp)); _raise_if_error()
+            return pp
+        ui = np.zeros(self.P, np.int32); pars = np.zeros(self.P, np.int32)
+        self.L.Get_Regraft_Partial_Pars(self.tree, ip(ui), ip(pars), None); _raise_if_error()
+        return ui, pars
+
+    def Get_Regraft_Site_Pars(self):
+        out = np.zeros(self.P, np.int32)
+        self.L.Get_Regraft_Site_Pars(self.tree, out.ctypes.data_as(C.c_void_p)); _raise_if_error()
+        return out
+
     @property
     def c_pars(self):
         return self.tree.contents.c_pars
