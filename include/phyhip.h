@@ -608,6 +608,33 @@ int phyhip_get_virtual_stats(int instance, long long out[4]);
    out[3].  None of them counts in phyhip_get_virtual_stats.  Sharded instances: the first shard's counters. */
 int phyhip_get_deferred_stats(int instance, long long out[4]);
 
+/* Chained buffers: the third class of unstored result.  The deferred class keeps a forwarded result stored whenever one of its
+   children is itself unstored, and a post-order is mostly chains (tip x cherry, then the result of the step before), so most
+   forwarded results stay stored only so that a later reader could find them in memory.  A launch of the list form with at least
+   `minOperations` operations (default 16; 0: off) in which NO TRANSITION MATRIX IS READ TWICE -- a one-sided traversal, the
+   Lk(NULL) that Generic_Brent_Lk repeats while a model parameter is optimised -- leaves such a result unstored as well: a child
+   may be a tip, a buffer in memory, or a buffer that is unstored after the launch (virtual, deferred, or chained earlier in the
+   list).  Nothing is recomputed inside the launch and no kernel differs; the stores go.  Both-sided traversals (post-order and
+   pre-order share the edge matrices) and the short launches of a search never chain.
+     The cost side: a chained definition is one step of a recursion, not one step over stored inputs.  Every definition of any
+   class carries a sequence number (inputs lower than dependants), and whatever stores a chained buffer -- the readers listed
+   above, the setters, a matrix without a free snapshot slot, a tip row -- stores its unstored inputs with it, transitively, in
+   that order, in front of the queue.  The first read of a buffer deep in a tree behind a one-sided traversal therefore launches up
+   to the whole traversal once more, storing ("a short launch that has to store one stores all": at most one all-stored traversal,
+   once); a repeated traversal launches nothing for the old definitions.  A later launch settles what earlier ones left, for the
+   deferred and the chained class by one rule: definitions whose buffer it reads first, or whose input buffer it writes while the
+   buffer itself stays, are stored in front together with their unstored inputs; definitions whose buffer it writes first are
+   dropped unless one of those needs them; the rest stays.  phyhip_set_virtual_buffers(0) stores all three classes and stops
+   all three; another threshold there does not move this one.  Values that leave through this interface are unchanged
+   (tests/test_gpu_chained.py).  Sharded instances: applied to every shard. */
+int phyhip_set_chained_buffers(int instance, int minOperations);
+
+/* The chained class: out[0] buffers chained right now, out[1] stores left out so far, out[2] definitions stored on demand, out[3]
+   definitions dropped.  out[1] = out[0] + out[2] + out[3].  They count neither in phyhip_get_virtual_stats nor in
+   phyhip_get_deferred_stats (a deferred or virtual input stored with a chained buffer counts in its own class).  Sharded
+   instances: the first shard's counters. */
+int phyhip_get_chained_stats(int instance, long long out[4]);
+
 /* ---- parsimony (src/pars.c) --------------------------------------------------------------------------------------------------- */
 
 /* Update_Partial_Pars (src/pars.c:239-393) and Pars / Pars_Core (src/pars.c:20-52, 397-437) on the device, in the reference's own

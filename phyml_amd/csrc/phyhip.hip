@@ -371,6 +371,10 @@ static int build_instance(Instance *I, const hipDeviceProp_t &prop)
   I->deferred.assign(I->nbuf, 0);
   I->ddef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
   I->defer_stores = I->nmat_all >= I->nmat + 2 * (I->nbuf - I->tips) && I->nbuf > I->tips;
+  // (chained buffers: the third class, on top of the deferred one -- one-sided lists of at least chain_min_ops operations)
+  I->chained.assign(I->nbuf, 0);
+  I->def_seq.assign(I->nbuf, 0);
+  I->chain_min_ops = I->defer_stores ? 16 : 0;
   HIPCHK(hipMalloc((void **)&I->d_ops, (size_t)I->ops_slots * I->ops_slot_bytes));
   size_t chunk = std::max<size_t>(64 * 1024, std::max(I->ops_slot_bytes,
                                                        (size_t)I->C * I->S * I->S * sizeof(double) * 4));
@@ -749,13 +753,12 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     if (idx[i] < 0 || idx[i] >= I->nmat) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "matrix index %d", idx[i]);
   bool queued_reader = false;
   for (int i = 0; i < count && !queued_reader; ++i) queued_reader = I->mat_in_queue[idx[i]] != 0;
-  // does an unstored buffer's definition -- virtual or deferred -- read one of them?  (a scan of the buffer flags: only while there are some)
-  auto is_def = [&](int b) { return I->n_deferred > 0 && I->deferred[b] != 0; };
+  // does an unstored buffer's definition -- virtual, deferred or chained -- read one of them?  (a scan of the buffer flags: only while there are some)
   auto depends = [&]() {
-    for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
-      if (I->virt[b] || is_def(b))
+    for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
+      if (is_unstored(I, b))
       {
-        const DevOp &d = I->virt[b] ? I->vdef[b] : I->ddef[b];
+        const DevOp &d = unstored_def(I, b);
         for (int i = 0; i < count; ++i)
           if (d.pm1 == idx[i] || d.pm2 == idx[i]) return true;
       }
@@ -769,8 +772,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     int rc = flush(I, nullptr);
     if (rc) return rc;
   }
-  if (I->n_virtual == 0 && I->n_deferred == 0) return 0;
-  const unsigned long long stored_before = I->n_virt_material + I->n_def_material;
+  if (n_unstored(I) == 0) return 0;
+  const unsigned long long stored_before = I->n_virt_material + I->n_def_material + I->n_chain_material;
   // A virtual buffer is defined on the matrices as they are.  Before one changes: pmat_kernel / upload_matrices_kernel move the
   // old value into the buffer's own snapshot slot, and the definition reads it there from now on (a full traversal that follows
   // recomputes every buffer anyway; the host route rewrites a tree's matrices one call at a time) -- or the buffer is stored first.
@@ -789,10 +792,10 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
         if (idx[i] == pm) return i;
       return -1;
     };
-    for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
+    for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
     {
-      if (!I->virt[b] && !is_def(b)) continue;
-      DevOp &d = I->virt[b] ? I->vdef[b] : I->ddef[b]; // (a deferred buffer's two snapshot slots are its own as well)
+      if (!is_unstored(I, b)) continue;
+      DevOp &d = unstored_def(I, b); // (a deferred or chained buffer's two snapshot slots are its own as well)
       const int  i1 = pos(d.pm1), i2 = pos(d.pm2);
       if (i1 < 0 && i2 < 0) continue;
       if (shadow->empty()) shadow->assign(count, -1);
@@ -805,8 +808,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     }
   }
   else
-    for (int i = 0; i < count && (I->n_virtual > 0 || I->n_deferred > 0); ++i) devirtualise_matrix(I, idx[i]);
-  if (I->n_virt_material + I->n_def_material != stored_before)
+    for (int i = 0; i < count && n_unstored(I) > 0; ++i) devirtualise_matrix(I, idx[i]);
+  if (I->n_virt_material + I->n_def_material + I->n_chain_material != stored_before)
   { // (stored on the old values: now)
     int rc = flush(I, nullptr);
     if (rc) return rc;
@@ -1320,7 +1323,7 @@ int phyhip_set_virtual_buffers(int instance, int minOperations)
   GET_INST(I, instance);
   if (minOperations < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "minOperations %d", minOperations);
   I->virt_min_ops = minOperations;
-  if (minOperations == 0 && (I->n_virtual > 0 || I->n_deferred > 0))
+  if (minOperations == 0 && n_unstored(I) > 0)
   {
     devirtualise_all(I);
     return flush(I, nullptr);
@@ -1342,6 +1345,23 @@ int phyhip_get_deferred_stats(int instance, long long out[4])
   if (Group *G = get_group(instance)) return phyhip_get_deferred_stats(G->sub_id[0], out);
   GET_INST(I, instance); // (an ordinary entry: the resident-aware queries are a reviewed list, tests/test_abi.py)
   out[0] = I->n_deferred; out[1] = (long long)I->n_def_skipped; out[2] = (long long)I->n_def_material; out[3] = (long long)I->n_def_dropped;
+  return PHYHIP_SUCCESS;
+}
+
+int phyhip_set_chained_buffers(int instance, int minOperations)
+{
+  if (Group *G = get_group(instance)) return group_each(G, [&](int id, long long, long long) { return phyhip_set_chained_buffers(id, minOperations); });
+  GET_INST(I, instance);
+  if (minOperations < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "minOperations %d", minOperations);
+  I->chain_min_ops = I->defer_stores ? minOperations : 0; // (what is chained now stays so until something needs it: the next list settles it)
+  return PHYHIP_SUCCESS;
+}
+
+int phyhip_get_chained_stats(int instance, long long out[4])
+{
+  if (Group *G = get_group(instance)) return phyhip_get_chained_stats(G->sub_id[0], out);
+  GET_INST(I, instance);
+  out[0] = I->n_chained; out[1] = (long long)I->n_chain_skipped; out[2] = (long long)I->n_chain_material; out[3] = (long long)I->n_chain_dropped;
   return PHYHIP_SUCCESS;
 }
 

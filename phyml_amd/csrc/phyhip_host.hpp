@@ -330,6 +330,20 @@ struct Instance
   std::vector<unsigned char>             deferred;          // [nbuf]
   std::vector<DevOp>                     ddef;              // [nbuf]
   unsigned long long                     n_def_skipped = 0, n_def_material = 0, n_def_dropped = 0; // phyhip_get_deferred_stats
+  // Chained buffers: the third class.  A one-sided list of at least chain_min_ops operations -- one in which no
+  // transition matrix is read twice -- leaves a forwarded result unstored also when a child is itself unstored after the launch
+  // (virtual, deferred, or chained earlier in the list): chained[b] != 0, the operation is in ddef[b] (a buffer is deferred or
+  // chained, never both).  Such definitions are ordered: every definition of any class carries a number from one counter
+  // (def_seq[b], from next_seq), so an input's is lower than its dependant's, and whatever stores a chained buffer stores its
+  // unstored inputs in front of it, transitively; the definitions standing in front of `pending` (the first n_front entries) are
+  // kept in ascending order of these numbers.  Off (chain_min_ops == 0, def_seq empty) in a hand-built Instance.
+  int                                    chain_min_ops = 0; // lists at least this long chain (0: never); phyhip_create_instance: 16
+  int                                    n_chained = 0;
+  int                                    n_front = 0;       // stored definitions at the head of `pending` (until it is launched: retire_queue, or rewritten as a long list)
+  std::vector<unsigned char>             chained;           // [nbuf]
+  std::vector<unsigned long long>        def_seq;           // [nbuf]
+  unsigned long long                     next_seq = 0;
+  unsigned long long                     n_chain_skipped = 0, n_chain_material = 0, n_chain_dropped = 0; // phyhip_get_chained_stats
   std::vector<int>                       pm_idx;    // queued device-side matrix rebuilds (index, edge length)
   std::vector<double>                    pm_len;
   std::vector<int>                       pm_slot;   // matrix index -> position in pm_idx, or -1
@@ -587,11 +601,11 @@ int  check_partial_index(const Instance *I, int idx, bool allow_tip);
 int  wait_host_sum(Instance *I);
 int  wait_result(Instance *I);
 int  collect_profile(Instance *I);
-void devirtualise(Instance *I, int buf);       // queue (in front) the storing operation that makes buffer `buf` real again
+void devirtualise(Instance *I, int buf);       // queue (in front) the storing operation that makes buffer `buf` real again, behind those of its unstored inputs
 void devirtualise_all(Instance *I);
 void devirtualise_matrix(Instance *I, int m);  // ... for every virtual buffer whose definition reads matrix m
 void devirtualise_tip(Instance *I, int tip);   // ... reads tip row `tip`
-void devirtualise_dependants(Instance *I, int buf); // ... for every deferred buffer whose definition reads buffer `buf` (about to be written outside the queue)
+void devirtualise_dependants(Instance *I, int buf); // ... for every deferred or chained buffer whose definition reads buffer `buf` (about to be written outside the queue)
 // snapshot slot w (0: the definition's first matrix, 1: its second) of internal buffer b in the matrix tables
 // (the launch in between has happened: nothing is asked to stay stored any more)
 inline void keep_real_clear(Instance *I)
@@ -600,6 +614,13 @@ inline void keep_real_clear(Instance *I)
   I->keep_real.clear();
 }
 inline int shadow_slot(const Instance *I, int b, int w) { return I->nmat + 2 * (b - I->tips) + w; }
+// the three classes of unstored buffer: virtual, deferred, chained -- and the definition of one (vdef, or ddef for the other two)
+inline int  n_unstored(const Instance *I) { return I->n_virtual + I->n_deferred + I->n_chained; }
+inline bool is_unstored(const Instance *I, int b)
+{
+  return I->virt[b] || (I->n_deferred > 0 && I->deferred[b]) || (I->n_chained > 0 && I->chained[b]);
+}
+inline DevOp &unstored_def(Instance *I, int b) { return I->virt[b] ? I->vdef[b] : I->ddef[b]; }
 void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise);
 
 // ---- resident evaluators: host side -----------------------------------------------------------------------------

@@ -10,69 +10,110 @@ namespace phyhip_host
 constexpr int kOpNoStore = 1; // DevOp::pad bit 0: the operation's result is forwarded in registers only (descriptors of size 0)
 constexpr int kOpInl1 = 2, kOpInl2 = 4; // DevOp::pad bits 1, 2: child 1 / child 2 is computed inside the operation's own step (Instance::pending_inl)
 
-void devirtualise(Instance *I, int buf)
+// The launch in between must leave the buffer in memory, whatever the queue does with it (rewrite_pending)
+static void keep_stored(Instance *I, int buf)
 {
-  // whoever asks is about to read the buffer from memory -- a kernel outside the traversal launch (eigen_lr_kernel, a mixture
-  // combination), a copy to the host, or a setter that changes what the buffer was computed from: the launch in between must not
-  // leave it virtual AGAIN (a long queue that writes it with a tip x tip operation and reads it later would: rewrite_pending)
   if (buf >= I->tips && buf < I->nbuf && I->virt_min_ops > 0 && !I->keep_real_flag[buf])
   { // (a flag per buffer + the list of the flagged ones: constant-time lookup in rewrite_pending, no duplicates)
     I->keep_real_flag[buf] = 1;
     I->keep_real.push_back(buf);
   }
-  if (I->n_deferred > 0 && buf >= I->tips && buf < I->nbuf && I->deferred[buf])
-  { // a deferred buffer: its definition reads tips, matrices and buffers that are in memory and have not been written since
-    // (rewrite_pending stores or drops it before one is) -- in front of the queue as well
-    DevOp op = I->ddef[buf];
-    op.pad   = 0;
-    I->pending.insert(I->pending.begin(), op);
-    I->mat_in_queue[op.pm1] = 1; I->mat_in_queue[op.pm2] = 1;
-    I->deferred[buf] = 0;
-    --I->n_deferred;
-    ++I->n_def_material;
-    return;
-  }
-  if (I->n_virtual == 0 || buf < I->tips || buf >= I->nbuf || !I->virt[buf]) return;
-  DevOp op = I->vdef[buf];
-  op.pad   = 0;
-  // in FRONT of what is queued: it reads tips and matrices only (unchanged since the launch that left it virtual), and a queued
-  // operation may read it
-  I->pending.insert(I->pending.begin(), op);
-  I->mat_in_queue[op.pm1] = 1; I->mat_in_queue[op.pm2] = 1;
-  I->virt[buf] = 0;
-  --I->n_virtual;
-  ++I->n_virt_material;
 }
 
-// (both classes of unstored buffer: virtual and deferred)
-static inline bool unstored(const Instance *I, int b) { return I->virt[b] || (I->n_deferred > 0 && I->deferred[b]); }
-static inline const DevOp &unstored_def(const Instance *I, int b) { return I->virt[b] ? I->vdef[b] : I->ddef[b]; }
+// The storing definition of one unstored buffer into the front of the queue.  A virtual definition reads tips, a deferred one
+// tips and buffers that have not been written since (rewrite_pending stores or drops it before one is); such a buffer may be
+// unstored itself -- under a chained definition, and under a deferred one made by a list that chains (defer_forwarded's second pass) -- and then
+// its definition goes in first, transitively.  With sequence numbers (Instance::def_seq) the definitions in front of the queue
+// stay in ascending order, so one queued by an earlier call that reads a buffer stored by this one still finds it written in
+// front of it; without them (a hand-built Instance, no chained class) each goes to the very front.
+static void store_definition(Instance *I, int buf)
+{
+  const bool v = I->virt[buf] != 0, ch = !v && I->n_chained > 0 && I->chained[buf];
+  DevOp      op = v ? I->vdef[buf] : I->ddef[buf];
+  op.pad = 0;
+  if (!v && I->n_chained > 0) // (a deferred definition's inputs were stored when it was made; a list that chains may have left one unstored behind it)
+    for (int c : {op.c1, op.c2})
+      if (c >= I->tips && is_unstored(I, c))
+      { // (stored for good, like the buffer that was asked for: whoever asked may be about to change a tip row or a matrix under it)
+        keep_stored(I, c);
+        store_definition(I, c);
+      }
+  size_t at = 0;
+  if (!I->def_seq.empty())
+  {
+    I->n_front = std::min(I->n_front, (int)I->pending.size());
+    while (at < (size_t)I->n_front && I->def_seq[I->pending[at].dest] < I->def_seq[buf]) ++at;
+    ++I->n_front;
+  }
+  I->pending.insert(I->pending.begin() + (long)at, op);
+  I->mat_in_queue[op.pm1] = 1; I->mat_in_queue[op.pm2] = 1;
+  if (v) { I->virt[buf] = 0; --I->n_virtual; ++I->n_virt_material; }
+  else if (ch) { I->chained[buf] = 0; --I->n_chained; ++I->n_chain_material; }
+  else { I->deferred[buf] = 0; --I->n_deferred; ++I->n_def_material; }
+}
+
+void devirtualise(Instance *I, int buf)
+{
+  // whoever asks is about to read the buffer from memory -- a kernel outside the traversal launch (eigen_lr_kernel, a mixture
+  // combination), a copy to the host, or a setter that changes what the buffer was computed from: the launch in between must not
+  // leave it virtual AGAIN (a long queue that writes it with a tip x tip operation and reads it later would: rewrite_pending)
+  keep_stored(I, buf);
+  if (buf < I->tips || buf >= I->nbuf || !is_unstored(I, buf)) return;
+  store_definition(I, buf);
+}
 
 void devirtualise_all(Instance *I)
 {
-  for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
-    if (unstored(I, b)) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
+    if (is_unstored(I, b)) devirtualise(I, b);
 }
 
 void devirtualise_matrix(Instance *I, int m)
 {
-  for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
-    if (unstored(I, b) && (unstored_def(I, b).pm1 == m || unstored_def(I, b).pm2 == m)) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
+    if (is_unstored(I, b) && (unstored_def(I, b).pm1 == m || unstored_def(I, b).pm2 == m)) devirtualise(I, b);
 }
 
 void devirtualise_tip(Instance *I, int tip)
 {
-  for (int b = I->tips; b < I->nbuf && (I->n_virtual > 0 || I->n_deferred > 0); ++b)
-    if (unstored(I, b) && (unstored_def(I, b).c1 == tip || unstored_def(I, b).c2 == tip)) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
+    if (is_unstored(I, b) && (unstored_def(I, b).c1 == tip || unstored_def(I, b).c2 == tip)) devirtualise(I, b);
 }
 
-// A buffer is about to be written by something that does not pass through the queue (a setter): deferred buffers whose
-// definitions read it are stored first, on its old value
+// A buffer is about to be written by something that does not pass through the queue (a setter): deferred and chained buffers whose
+// definitions read it are stored first, on its old value (their own dependants then read them from memory)
 void devirtualise_dependants(Instance *I, int buf)
 {
   if (buf < I->tips) return;
-  for (int b = I->tips; b < I->nbuf && I->n_deferred > 0; ++b)
-    if (I->deferred[b] && (I->ddef[b].c1 == buf || I->ddef[b].c2 == buf)) devirtualise(I, b);
+  for (int b = I->tips; b < I->nbuf && I->n_deferred + I->n_chained > 0; ++b)
+    if (!I->virt[b] && is_unstored(I, b) && (I->ddef[b].c1 == buf || I->ddef[b].c2 == buf)) devirtualise(I, b);
+}
+
+// settle_deferred with chained definitions about: one rule for the deferred and the chained class.  For the definition d of b --
+// needed: b is read before it is written; dead: b is written before it is read.  M0 = {needed} + {not dead, and the list writes
+// one of d's input buffers}; M = M0 closed under "unstored input of a member" (store_definition's recursion).  M is stored in
+// front, in sequence order; dead definitions outside M are dropped; the rest stays.  A kept definition cannot have a dropped
+// input: the list writes that input, which puts the dependant into M0.  (A dead input in M is stored and overwritten later.)
+static bool settle_chained(Instance *I, const std::vector<int> &first_read, const std::vector<int> &first_write, int never)
+{
+  auto written = [&](int c) { return c >= I->tips && first_write[c] != never; };
+  const unsigned long long before = I->n_virt_material + I->n_def_material + I->n_chain_material;
+  std::vector<int> m0;
+  for (int b = I->tips; b < I->nbuf; ++b)
+  {
+    if (I->virt[b] || !is_unstored(I, b)) continue;
+    const bool needed = first_read[b] < first_write[b], dead = !needed && first_write[b] != never;
+    if (needed || (!dead && (written(I->ddef[b].c1) || written(I->ddef[b].c2)))) m0.push_back(b);
+  }
+  for (int b : m0)
+    if (is_unstored(I, b)) devirtualise(I, b); // (an earlier member's closure may have stored it)
+  for (int b = I->tips; b < I->nbuf && I->n_deferred + I->n_chained > 0; ++b)
+  {
+    if (I->virt[b] || !is_unstored(I, b) || first_write[b] == never) continue; // (what is still flagged is not needed: dead)
+    if (I->deferred[b]) { I->deferred[b] = 0; --I->n_deferred; ++I->n_def_dropped; }
+    else { I->chained[b] = 0; --I->n_chained; ++I->n_chain_dropped; }
+  }
+  return I->n_virt_material + I->n_def_material + I->n_chain_material != before;
 }
 
 // Deferred buffers left by earlier launches against the list that is about to run and its evaluation, in order.  The list reads
@@ -82,10 +123,12 @@ void devirtualise_dependants(Instance *I, int buf)
 // (a short launch then stores them all: it is a list now in any case, and the short launches behind it keep their form).
 static bool settle_deferred(Instance *I, const EdgeEval *ee)
 {
-  if (I->n_deferred == 0) return false;
+  if (I->n_deferred == 0 && I->n_chained == 0) return false;
   const int        n0 = (int)I->pending.size(), never = n0 + 1;
   std::vector<int> first_read(I->nbuf, never), first_write(I->nbuf, never);
-  for (int k = 0; k < n0; ++k)
+  // (chained definitions about: the stored definitions already standing in front write values their dependants are defined on --
+  // making an input real does not invalidate a dependant)
+  for (int k = I->n_chained > 0 ? std::min(I->n_front, n0) : 0; k < n0; ++k)
   {
     const DevOp &o = I->pending[k];
     for (int c : {o.c1, o.c2})
@@ -95,6 +138,7 @@ static bool settle_deferred(Instance *I, const EdgeEval *ee)
   if (ee)
     for (int c : {ee->parent, ee->child})
       if (c >= I->tips && first_read[c] == never) first_read[c] = n0;
+  if (I->n_chained > 0) return settle_chained(I, first_read, first_write, never);
   bool stored = false;
   auto written = [&](int c) { return c >= I->tips && first_write[c] != never; };
   for (int b = I->tips; b < I->nbuf && I->n_deferred > 0; ++b)
@@ -107,12 +151,43 @@ static bool settle_deferred(Instance *I, const EdgeEval *ee)
   return stored;
 }
 
+// (every definition of an unstored buffer, of any class, in the order they are made: Instance::def_seq)
+static inline void stamp_definition(Instance *I, int b)
+{
+  if (!I->def_seq.empty()) I->def_seq[b] = ++I->next_seq;
+}
+
+// Does the list qualify for the chained class?  At least chain_min_ops operations, virtual buffers on, and no transition matrix
+// read twice (one-sided traversals: in a both-sided one the post-order and the pre-order share the edge matrices, and each refresh
+// of one would store whole closures -- matrices_touch).
+static bool list_chains(const Instance *I, const std::vector<DevOp> &L, const std::vector<InlineDef> &LI)
+{
+  const int n = (int)L.size();
+  if (I->chain_min_ops <= 0 || n < I->chain_min_ops || I->virt_min_ops <= 0 || I->chained.empty()) return false;
+  std::vector<unsigned char> seen(I->mat_in_queue.size(), 0);
+  auto twice = [&](int m) { if (m < 0) return false; if (seen[m]) return true; seen[m] = 1; return false; };
+  for (int k = 0; k < n; ++k)
+  {
+    if (twice(L[k].pm1) || twice(L[k].pm2)) return false;
+    if ((L[k].pad & (kOpInl1 | kOpInl2)) && (twice(LI[k].pmA) || twice(LI[k].pmB))) return false;
+  }
+  return true;
+}
+
 // Deferred buffers, the rule (on the list as it will be launched, front to back): a storing operation whose destination is written
 // once in the list, read in it only by the next two operations -- exactly the reads child_descs forwards in registers -- and
 // neither read by the evaluation nor asked for from memory (keep_real) does not store, if each child is a tip or a buffer that is
 // in memory after this launch: not virtual, not computed in-step, not deferred, not written again behind the operation.  So every
-// deferred definition is ONE step over stored inputs: no recursion and no order among definitions.
-static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> &L)
+// deferred definition is made as ONE step over stored inputs, and in a list that does not chain it stays so: no recursion and no
+// order among definitions.
+// Chained buffers (`chain`: list_chains), a second pass with the same conditions over what the first left storing, but for the
+// children: a child may be a tip or ANY buffer that is not written again behind the operation.  It is then either in memory
+// after this launch, or unstored under a definition that computes the value this operation read -- virtual (read in-step or
+// through a re-issue; a list writes a buffer it leaves virtual once), deferred, or chained earlier in this list.  In such a list a
+// result deferred by the first pass may see one of its stored inputs chained by the second (it is one of that input's two readers):
+// then the deferred definition reads an unstored buffer too, and its sequence number is renewed so that the definitions of the
+// list are numbered in list order, inputs before dependants (store_definition follows the inputs of both classes).
+static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> &L, bool chain)
 {
   const int        n = (int)L.size();
   std::vector<int> n_dest(I->nbuf, 0), last_write(I->nbuf, -1), last_read(I->nbuf, -1);
@@ -129,21 +204,25 @@ static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> 
   auto in_memory = [&](int c, bool in_step, int i) {
     return c < I->tips || (!in_step && !I->virt[c] && !I->deferred[c] && last_write[c] < i);
   };
-  for (int i = 0; i + 1 < n; ++i)
-  {
-    DevOp &o = L[i];
-    if ((o.pad & kOpNoStore) || n_dest[o.dest] != 1) continue;
-    if (last_read[o.dest] <= i || last_read[o.dest] > i + 2) continue; // (never read behind it, or read from memory)
-    if ((ee && (ee->parent == o.dest || ee->child == o.dest)) || I->keep_real_flag[o.dest]) continue;
-    if (!in_memory(o.c1, o.pad & kOpInl1, i) || !in_memory(o.c2, o.pad & kOpInl2, i)) continue;
-    if (i + 3 == n && (pad_read1 == o.dest || pad_read2 == o.dest)) continue; // (the odd-list rule, for this class)
-    I->ddef[o.dest] = o;
-    I->ddef[o.dest].pad = 0;
-    I->deferred[o.dest] = 1;
-    ++I->n_deferred;
-    ++I->n_def_skipped;
-    o.pad |= kOpNoStore;
-  }
+  auto not_rewritten = [&](int c, int i) { return c < I->tips || last_write[c] < i; };
+  for (int pass = 0; pass < (chain ? 2 : 1); ++pass)
+    for (int i = 0; i + 1 < n; ++i)
+    {
+      DevOp &o = L[i];
+      if (pass == 1 && (o.pad & kOpNoStore) && !I->virt[o.dest] && I->deferred[o.dest]) stamp_definition(I, o.dest); // (deferred by pass 0)
+      if ((o.pad & kOpNoStore) || n_dest[o.dest] != 1) continue;
+      if (last_read[o.dest] <= i || last_read[o.dest] > i + 2) continue; // (never read behind it, or read from memory)
+      if ((ee && (ee->parent == o.dest || ee->child == o.dest)) || I->keep_real_flag[o.dest]) continue;
+      if (pass == 0 && (!in_memory(o.c1, o.pad & kOpInl1, i) || !in_memory(o.c2, o.pad & kOpInl2, i))) continue;
+      if (pass == 1 && (!not_rewritten(o.c1, i) || !not_rewritten(o.c2, i))) continue;
+      if (i + 3 == n && (pad_read1 == o.dest || pad_read2 == o.dest)) continue; // (the odd-list rule, for this class)
+      I->ddef[o.dest] = o;
+      I->ddef[o.dest].pad = 0;
+      if (pass == 0) { I->deferred[o.dest] = 1; ++I->n_deferred; ++I->n_def_skipped; }
+      else { I->chained[o.dest] = 1; ++I->n_chained; ++I->n_chain_skipped; }
+      stamp_definition(I, o.dest);
+      o.pad |= kOpNoStore;
+    }
 }
 
 // The queue as it will be launched.  Short lists (or kernels without two-deep forwarding): the first one that reads a virtual
@@ -167,7 +246,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
     for (const DevOp &o : I->pending) stay += !(o.c1 < I->tips && o.c2 < I->tips);
     virtualise = stay >= 3;
   }
-  if (!virtualise && I->n_virtual == 0 && I->n_deferred == 0) return;
+  if (!virtualise && n_unstored(I) == 0) return;
   if (!virtualise)
   { // A short launch.  If it reads a virtual buffer, EVERY virtual buffer is stored now, in this one launch: the short launches
     // of a tree search (SPR candidates, Lk(b), Br_Len_Opt) come in long runs after a full traversal, and one list of tip x tip
@@ -234,6 +313,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
       if (!I->virt[o.dest]) { I->virt[o.dest] = 1; ++I->n_virtual; }
       o.pad = 0;
       I->vdef[o.dest] = o;
+      stamp_definition(I, o.dest);
       ++I->n_virt_skipped;
       continue;
     }
@@ -267,9 +347,13 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
       if (I->virt[d1.dest]) { I->virt[d1.dest] = 0; --I->n_virtual; ++I->n_virt_material; }
     }
   }
-  if (I->defer_stores) defer_forwarded(I, ee, L);
+  if (I->defer_stores) defer_forwarded(I, ee, L, list_chains(I, L, LI));
   I->pending.swap(L);
   if (any_inl) I->pending_inl.swap(LI);
+  // (the rewritten list is launched as it stands: flush_impl.  A SHORT list leaves here as it came, its stored definitions still
+  // in front and n_front still counting them -- phyhip_update_eigen_lr rewrites its queue once without launching and the flush
+  // rewrites it again: the second settle_deferred must still know them, and a definition stored then must still find its place)
+  I->n_front = 0;
 }
 
 // Host-computed matrices queued by phyhip_set_transition_matrix: one launch per kUploadBatch of them.
@@ -465,6 +549,7 @@ static void retire_queue(Instance *I, bool fold_pm)
     I->pm_shadow.clear();
   }
   I->pending.clear();
+  I->n_front = 0;
   std::fill(I->mat_in_queue.begin(), I->mat_in_queue.end(), 0);
 }
 

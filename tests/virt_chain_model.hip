@@ -1,0 +1,477 @@
+// tests/virt_chain_model.hip -- test infrastructure (CPU only, no device is touched): the symbolic model of tests/virt_defer_model.hip
+// with the CHAINED class of unstored buffer switched on (Instance::chain_min_ops, chained, def_seq; phyml_amd/csrc/phyhip_queue.hip:
+// defer_forwarded's second pass, settle_chained, store_definition).  It links the BUILT library, builds an Instance by hand, feeds it random queues,
+// readers and writers, and after every "launch" interprets the rewritten queue with the kernels' forwarding rules (last two results
+// in registers, in-step children, non-storing operations) on symbolic values, in lockstep with the plain semantics.  After every
+// launch:
+//   * the definition of every unstored buffer, evaluated over its inputs' definitions recursively (stored inputs: device memory),
+//     is the buffer's plain value;
+//   * every input of a deferred or chained definition is a tip, stored, or unstored under an older sequence number (a deferred
+//     definition is made over stored inputs; a list that chains may leave one of them chained behind it);
+//   * every written buffer is stored or unstored; a reader finds the plain value in memory; the counters match the flags.
+// Events: replayed post-orders in which every edge has its own matrix (the lists that chain), random long and short lists, short
+// lists that write a buffer in the middle of a chain (the buffer itself or one of its inputs), a reader of a chain's last buffer
+// before any reader of its first -- across launches and inside one queue, in both orders --, readers that rewrite the queue once
+// without launching it before the launch rewrites it again (phyhip_update_eigen_lr), tip and matrix changes, threshold moves.
+// Built and run by tests/test_virt_chain_model.py:  virt_chain_model <seed> <events> <tips> <soa 0|1> [in-step children 1|0]
+#include "../phyml_amd/csrc/phyhip_host.hpp"
+
+#include <algorithm>
+#include <cstdint>
+#include <random>
+
+using namespace phyhip_host;
+
+static uint64_t H(uint64_t a, uint64_t b, uint64_t c, uint64_t d)
+{
+  uint64_t x = 0x9e3779b97f4a7c15ull;
+  for (uint64_t v : {a, b, c, d})
+  {
+    x ^= v + 0x9e3779b97f4a7c15ull + (x << 6) + (x >> 2);
+    x *= 0xbf58476d1ce4e5b9ull;
+    x ^= x >> 31;
+  }
+  return x;
+}
+
+struct Model
+{
+  Instance *I;
+  std::vector<uint64_t> tipv, matv;     // versions of the tip rows / matrices
+  std::vector<uint64_t> ref, dev;       // plain semantics / device memory per buffer
+  std::vector<char>     written;        // the buffer has been the destination of a queued operation
+  std::vector<DevOp>    queued;         // what the caller queued since the last launch (plain semantics are applied at launch)
+  long                  n_launch = 0, n_instep = 0, n_nostore = 0, n_pad = 0;
+  mutable long          max_chain = 0;
+
+  uint64_t tipval(int t) const { return H(1, (uint64_t)t, tipv[t], 0); }
+  uint64_t def_value(const DevOp &d) const { return H(tipval(d.c1), tipval(d.c2), matv[d.pm1], matv[d.pm2]); }
+
+  // what a buffer IS after a launch: device memory, or its definition over what its inputs are
+  uint64_t value(int c, int depth = 0) const
+  {
+    if (c < I->tips) return tipval(c);
+    if (!is_unstored(I, c)) return dev[c];
+    if (depth > I->nbuf) die("definitions form a cycle", c);
+    const DevOp &d = unstored_def(I, c);
+    return H(value(d.c1, depth + 1), value(d.c2, depth + 1), matv[d.pm1], matv[d.pm2]);
+  }
+
+  [[noreturn]] void die(const char *what, int a = -1, int b = -1) const
+  {
+    fprintf(stderr, "VIRT_CHAIN_MODEL FAIL: %s (%d, %d) after %ld launches\n", what, a, b, n_launch);
+    exit(1);
+  }
+
+  // One launch.  Every queued operation carries its number in the upper bits of DevOp::pad (the library uses bits 0-2 and copies
+  // the rest along), so the device's run of the REWRITTEN queue can be followed in lockstep with the plain semantics (every
+  // operation stored, in queue order): `cur` is the plain value of every buffer at the point the device has reached.
+  void launch(const EdgeEval *ee)
+  {
+    std::vector<uint64_t> cur = ref;
+    size_t jp = 0;
+    auto plain = [&](size_t upto) { // apply the queued operations jp .. upto - 1
+      for (; jp < upto; ++jp)
+      {
+        const DevOp &o = queued[jp];
+        const uint64_t v1 = o.c1 < I->tips ? tipval(o.c1) : cur[o.c1], v2 = o.c2 < I->tips ? tipval(o.c2) : cur[o.c2];
+        cur[o.dest] = H(v1, v2, matv[o.pm1], matv[o.pm2]);
+      }
+    };
+    rewrite_pending(I, ee, true);
+    keep_real_clear(I); // (as flush_impl does)
+    const std::vector<DevOp> &L = I->pending;
+    const bool has_inl = !I->pending_inl.empty();
+    if (has_inl && I->pending_inl.size() != L.size()) die("pending_inl is not parallel to pending");
+    int      d1 = -1, d2 = -1; // destinations of the previous two operations
+    uint64_t r1 = 0, r2 = 0;   // ... and their results (registers)
+    for (size_t k = 0; k < L.size(); ++k)
+    {
+      const DevOp &o = L[k];
+      const size_t tag = (size_t)((unsigned)o.pad >> 8);
+      if ((o.pad & 6) && L.size() < 3) die("in-step child in a launch of the argument form", (int)k);
+      if ((o.pad & 1) && L.size() < 3) die("non-storing operation in a launch of the argument form", (int)k);
+      if (tag)
+      { // a queued operation at its place: everything queued in front of it has happened in the plain semantics (also the
+        // operations that left their place), it has not yet
+        if (tag - 1 < jp || tag - 1 >= queued.size()) die("queued operations out of order", (int)k, (int)tag);
+        plain(tag - 1);
+      }
+      else
+      { // an operation the library put in: it belongs to the queued operation that follows it (a definition re-issued in front of
+        // its reader: what left its place in front of that reader has happened), or to the end of the queue
+        size_t nxt = 0;
+        for (size_t j = k + 1; j < L.size() && !nxt; ++j) nxt = (size_t)((unsigned)L[j].pad >> 8);
+        if (nxt && nxt - 1 < jp) die("queued operations out of order", (int)k, (int)nxt);
+        plain(nxt ? nxt - 1 : queued.size());
+      }
+      auto child = [&](int c, int bit) -> uint64_t {
+        uint64_t v;
+        if (o.pad & bit)
+        {
+          if (!has_inl) die("in-step flag without a definition", (int)k);
+          const InlineDef &d = I->pending_inl[k];
+          if (d.a < 0 || d.a >= I->tips || d.b < 0 || d.b >= I->tips) die("in-step definition is not tip x tip", (int)k);
+          ++n_instep;
+          v = H(tipval(d.a), tipval(d.b), matv[d.pmA], matv[d.pmB]);
+        }
+        else if (c < I->tips) return tipval(c);
+        else if (c == d1) v = r1;
+        else if (c == d2) v = r2;
+        else v = dev[c];
+        if (v != cur[c]) die("an operation reads another value than the plain semantics hold at that point (stale memory, a stale register or a stale definition)", c, (int)k);
+        return v;
+      };
+      const uint64_t v = H(child(o.c1, 2), child(o.c2, 4), matv[o.pm1], matv[o.pm2]);
+      if (tag) plain(tag); // (the operation itself)
+      if (v != cur[o.dest]) die("an operation computes another value than the plain semantics hold for its buffer at that point", o.dest, (int)k);
+      if (o.pad & 1) ++n_nostore;
+      else dev[o.dest] = v;
+      d2 = d1; r2 = r1; d1 = o.dest; r1 = v;
+    }
+    plain(queued.size());
+    if ((L.size() & 1) && L.size() >= 3)
+    { // The pipelined kernels alternate two register sets: an odd LIST (three operations or more; shorter ones travel in the kernel
+      // arguments and are not padded) runs its last operation once more, one position later -- its own result is now the newest
+      // register, the previous operation's the second, and what was two steps back is gone: read from memory
+      const size_t k = L.size() - 1;
+      const DevOp &o = L[k];
+      ++n_pad;
+      auto child = [&](int c, int bit) -> uint64_t {
+        uint64_t v;
+        if (o.pad & bit)
+        {
+          const InlineDef &d = I->pending_inl[k];
+          v = H(tipval(d.a), tipval(d.b), matv[d.pmA], matv[d.pmB]);
+        }
+        else if (c < I->tips) return tipval(c);
+        else if (c == d2) v = r2; // (the operation in front of the last one)
+        else v = dev[c];
+        if (v != cur[c]) die("the re-run of an odd list's last operation reads a stale value", c, (int)k);
+        return v;
+      };
+      const uint64_t v = H(child(o.c1, 2), child(o.c2, 4), matv[o.pm1], matv[o.pm2]);
+      if (v != cur[o.dest]) die("the re-run of an odd list's last operation computes another value", o.dest, (int)k);
+      if (!(o.pad & 1)) dev[o.dest] = v;
+      r1 = v;
+    }
+    if (ee)
+      for (int side : {ee->parent, ee->child})
+      {
+        if (side < I->tips) continue;
+        const uint64_t seen = (side == d1) ? r1 : dev[side];
+        if (seen != cur[side]) die("the evaluation sees another value than the plain semantics", side);
+      }
+    std::vector<char> dest_now(I->nbuf, 0);
+    for (const DevOp &o : queued) dest_now[o.dest] = 1;
+    ref = cur;
+    queued.clear();
+    I->pending.clear();
+    I->n_front = 0; // (as retire_queue does)
+    std::fill(I->mat_in_queue.begin(), I->mat_in_queue.end(), 0);
+    ++n_launch;
+    // memory and definitions after the launch
+    int nv = 0;
+    for (int b = I->tips; b < I->nbuf; ++b)
+    {
+      if (I->virt[b])
+      {
+        ++nv;
+        const DevOp &d = I->vdef[b];
+        if (d.c1 >= I->tips || d.c2 >= I->tips) die("a virtual buffer's definition is not tip x tip", b);
+        if (def_value(d) != ref[b]) die("a virtual buffer's definition is not its plain value", b);
+      }
+      else if (!is_unstored(I, b) && written[b] && dev[b] != ref[b]) die("a buffer is neither stored nor unstored", b);
+    }
+    if (nv != I->n_virtual) die("n_virtual does not count the flags", nv, I->n_virtual);
+    int nd = 0, nc = 0;
+    for (int b = I->tips; b < I->nbuf; ++b)
+    {
+      if (I->deferred[b] + I->chained[b] + I->virt[b] > 1) die("a buffer is in two classes", b);
+      if (I->deferred[b])
+      {
+        ++nd;
+        const DevOp &d = I->ddef[b];
+        if (d.pad != 0) die("a deferred definition carries flags", b);
+        for (int c : {d.c1, d.c2})
+          if (c >= I->tips && I->virt[c]) die("a deferred definition reads a virtual buffer", b, c);
+      }
+      if (I->deferred[b] || I->chained[b])
+        for (int c : {I->ddef[b].c1, I->ddef[b].c2})
+        { // (a deferred definition is made over stored inputs; a list that chains may leave one of them chained behind it)
+          if (c < I->tips) continue;
+          if (is_unstored(I, c) ? I->def_seq[c] >= I->def_seq[b] : (!written[c] || dev[c] != ref[c]))
+            die("a definition's input is neither stored nor unstored under an older sequence number", b, c);
+        }
+      if (I->chained[b])
+      {
+        ++nc;
+        const DevOp &d = I->ddef[b];
+        if (d.pad != 0) die("a chained definition carries flags", b);
+        int len = 1; // (the longest chain of definitions that read buffers, ending in a chained one: a figure)
+        for (int c = b;;)
+        {
+          const DevOp &e = I->ddef[c];
+          auto link = [&](int x) { return x >= I->tips && (I->chained[x] || I->deferred[x]); };
+          const int nx = link(e.c1) ? e.c1 : link(e.c2) ? e.c2 : -1;
+          if (nx < 0) break;
+          c = nx; ++len;
+        }
+        max_chain = std::max(max_chain, (long)len);
+      }
+      if (is_unstored(I, b) && value(b) != ref[b]) die("an unstored buffer's definition, evaluated over its inputs' definitions, is not its plain value", b);
+    }
+    if (nd != I->n_deferred) die("n_deferred does not count the flags", nd, I->n_deferred);
+    if (nc != I->n_chained) die("n_chained does not count the flags", nc, I->n_chained);
+    if (I->n_def_skipped != (unsigned long long)I->n_deferred + I->n_def_material + I->n_def_dropped)
+      die("deferred counters: deferred so far != deferred now + stored on demand + dropped");
+    if (I->n_chain_skipped != (unsigned long long)I->n_chained + I->n_chain_material + I->n_chain_dropped)
+      die("chained counters: chained so far != chained now + stored on demand + dropped");
+  }
+};
+
+int main(int argc, char **argv)
+{
+  const unsigned seed = argc > 1 ? (unsigned)atoi(argv[1]) : 1u;
+  const int      events = argc > 2 ? atoi(argv[2]) : 2000, tips = argc > 3 ? atoi(argv[3]) : 12;
+  const bool     soa = argc > 4 ? atoi(argv[4]) != 0 : true;
+  const bool     in_step = argc > 5 ? atoi(argv[5]) != 0 : true; // 0: every virtual child re-issued as a step of its own (diag: PHYHIP_VIRT_INLINE=0)
+  std::mt19937   rng(seed);
+  auto rnd = [&](int n) { return (int)(rng() % (unsigned)n); };
+
+  Instance *I = new Instance();
+  I->tips = tips; I->nbuf = 3 * tips; I->nmat = 4 * tips + 2; I->nmat_all = I->nmat + 2 * (I->nbuf - I->tips);
+  I->S = soa ? 4 : 20; I->C = 4; I->soa = soa; I->perm = !soa; I->nt_groups = 2; I->prefetch_dist = 2;
+  I->virt.assign(I->nbuf, 0);
+  I->keep_real_flag.assign(I->nbuf, 0);
+  I->vdef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
+  I->mat_in_queue.assign(I->nmat_all, 0);
+  I->virt_min_ops = 3 + rnd(6);
+  I->deferred.assign(I->nbuf, 0);
+  I->ddef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
+  I->defer_stores = true;
+  I->chained.assign(I->nbuf, 0);
+  I->def_seq.assign(I->nbuf, 0);
+  I->chain_min_ops = 3 + rnd(6);
+  I->virt_inline = in_step;
+
+  Model M;
+  M.I = I;
+  M.tipv.assign(tips, 1); M.matv.assign(I->nmat_all, 1);
+  M.ref.assign(I->nbuf, 0); M.dev.assign(I->nbuf, 0); M.written.assign(I->nbuf, 0);
+
+  auto queue_op = [&](int dest, int c1, int c2, int pm1 = -1, int pm2 = -1) {
+    DevOp o{dest, c1, c2, pm1 < 0 ? rnd(I->nmat) : pm1, pm2 < 0 ? rnd(I->nmat) : pm2, 0};
+    M.queued.push_back(o);
+    o.pad = (int)(M.queued.size() << 8); // (its number in this queue, above the library's bits)
+    I->pending.push_back(o);
+    I->mat_in_queue[o.pm1] = 1; I->mat_in_queue[o.pm2] = 1;
+    M.written[dest] = 1;
+  };
+  auto any_child = [&](int not_this) {
+    for (;;)
+    {
+      const int c = rnd(I->nbuf);
+      if (c == not_this) continue;
+      if (c >= tips && !M.written[c]) continue; // (never written: the reference would read garbage as well)
+      return c;
+    }
+  };
+  // a "traversal": cherries first, then operations that read earlier results -- the shape that leaves buffers virtual
+  auto queue_traversal = [&](int n) {
+    std::vector<int> made;
+    for (int k = 0; k < n; ++k)
+    {
+      const int dest = tips + rnd(I->nbuf - tips);
+      const int kind = rnd(4);
+      // (an operation never reads its own destination: phyhip_update_partials refuses it)
+      int from = made.empty() ? -1 : made[rnd((int)made.size())];
+      if (from == dest) from = -1;
+      if (kind == 0 || from < 0) queue_op(dest, rnd(tips), rnd(tips));
+      else if (kind == 1) queue_op(dest, from, rnd(tips));
+      else queue_op(dest, from, any_child(dest));
+      if (std::find(made.begin(), made.end(), dest) == made.end()) made.push_back(dest);
+    }
+  };
+  // A post-order over distinct buffers, as Post_Order_Lk emits one: every result is read once, mostly by one of the next two
+  // operations; each edge has its own matrix.  Replayed, it rewrites inputs and buffers in the same order -- a repeated Lk(NULL).
+  std::vector<std::vector<DevOp>> orders;
+  auto make_order = [&]() {
+    std::vector<int> bufs;
+    for (int b = tips; b < I->nbuf; ++b) bufs.push_back(b);
+    std::shuffle(bufs.begin(), bufs.end(), rng);
+    const int n = std::min((int)bufs.size(), 3 + rnd(2 * tips - 3 > 0 ? 2 * tips - 3 : 1));
+    std::vector<DevOp> ops;
+    std::vector<int>   open; // results nobody has read yet
+    std::vector<int>   mats; // (every edge has its own matrix: a one-sided traversal, the lists that chain)
+    for (int m = 0; m < I->nmat; ++m) mats.push_back(m);
+    std::shuffle(mats.begin(), mats.end(), rng);
+    for (int k = 0; k < n; ++k)
+    {
+      auto take = [&](bool newest) {
+        if (open.empty() || rnd(3) == 0) return rnd(tips);
+        const size_t at = (newest || rnd(3)) ? open.size() - 1 : (size_t)rnd((int)open.size());
+        const int    c = open[at];
+        open.erase(open.begin() + (long)at);
+        return c;
+      };
+      const int c1 = take(true), c2 = take(false);
+      ops.push_back(DevOp{bufs[k], c1, c2, mats[2 * k], mats[2 * k + 1], 0});
+      open.push_back(bufs[k]);
+    }
+    return ops;
+  };
+  for (int k = 0; k < 3; ++k) orders.push_back(make_order());
+  // a buffer whose definition reads buffers (deferred or chained); the ends of the chained definitions by sequence number
+  auto any_dependant = [&]() {
+    std::vector<int> d;
+    for (int b = tips; b < I->nbuf; ++b)
+      if ((I->deferred[b] || I->chained[b]) && (I->ddef[b].c1 >= tips || I->ddef[b].c2 >= tips)) d.push_back(b);
+    return d.empty() ? -1 : d[rnd((int)d.size())];
+  };
+  auto chain_end = [&](bool last) {
+    int e = -1;
+    for (int b = tips; b < I->nbuf; ++b)
+      if (I->chained[b] && (e < 0 || (last ? I->def_seq[b] > I->def_seq[e] : I->def_seq[b] < I->def_seq[e]))) e = b;
+    return e;
+  };
+  // phyhip_update_eigen_lr stores what its products read, rewrites the queue ONCE WITHOUT LAUNCHING (a short list: it decides on
+  // the queue as it will be launched) and flushes afterwards, which rewrites it again: the reader events do the same half of the time
+  long n_double = 0;
+  auto reader = [&](int b) {
+    devirtualise(I, b);
+    if (rnd(2)) { rewrite_pending(I, nullptr, false); ++n_double; }
+  };
+  auto read_back = [&](int b, const char *what) {
+    if (is_unstored(I, b) || M.dev[b] != M.ref[b]) M.die(what, b);
+  };
+  long n_input_writes = 0, n_replays = 0, n_mid_writes = 0, n_end_reads = 0;
+  for (int ev = 0; ev < events; ++ev)
+  {
+    switch (rnd(17))
+    {
+      case 10: case 11: case 14:
+      { // a post-order traversal with its evaluation at the root, now and then a new one
+        if (rnd(8) == 0) orders[rnd((int)orders.size())] = make_order();
+        const std::vector<DevOp> &ops = orders[rnd((int)orders.size())];
+        for (const DevOp &o : ops) queue_op(o.dest, o.c1, o.c2, o.pm1, o.pm2);
+        ++n_replays;
+        if (rnd(4))
+        {
+          EdgeEval ee{ops.back().dest, rnd(tips), rnd(I->nmat), nullptr, true, nullptr};
+          M.launch(&ee);
+        }
+        else M.launch(nullptr);
+        break;
+      }
+      case 12: case 13:
+      { // a short list writes an input of a deferred or chained buffer (Update_Partial_Lk on the way of a search) -- a buffer in the
+        // middle of a chain, when the input is chained itself; then a reader of the dependant
+        const int b = any_dependant();
+        if (b < 0) break;
+        const DevOp d = I->ddef[b];
+        const int   c = d.c1 >= tips ? d.c1 : d.c2;
+        M.launch(nullptr);
+        if (!I->deferred[b] && !I->chained[b]) break;
+        const uint64_t old = M.ref[b];
+        n_mid_writes += is_unstored(I, c);
+        if (rnd(2)) queue_op(c, rnd(tips), rnd(tips));
+        else
+        {
+          queue_op(c, any_child(c), rnd(tips));
+          const int up = tips + rnd(I->nbuf - tips); // (... and the buffer above it, as the path of an SPR move does)
+          if (up != c && rnd(2)) queue_op(up, c, rnd(tips));
+        }
+        ++n_input_writes;
+        M.launch(nullptr);
+        if (M.queued.empty() && M.ref[b] == old && rnd(2))
+        {
+          reader(b);
+          M.launch(nullptr);
+          if (is_unstored(I, b) || M.dev[b] != old) M.die("an unstored buffer whose input was rewritten does not read back its old value", b, c);
+        }
+        break;
+      }
+      case 15: case 16:
+      { // readers of a chain's two ends: the last buffer before any reader of the first (across launches), or both inside one queue
+        // -- first then last (the last one's closure finds the first already queued), or last then first
+        M.launch(nullptr);
+        const int first = chain_end(false), last = chain_end(true);
+        if (first < 0 || first == last) break;
+        ++n_end_reads;
+        switch (rnd(3))
+        {
+          case 0:
+            reader(last); M.launch(nullptr); read_back(last, "a reader of a chain's last buffer finds it unstored or stale");
+            reader(first); M.launch(nullptr); read_back(first, "a reader of a chain's first buffer, behind one of its last, finds it unstored or stale");
+            break;
+          case 1: reader(first); reader(last); M.launch(nullptr); break;
+          default: reader(last); reader(first); M.launch(nullptr); break;
+        }
+        read_back(first, "a chain's first buffer does not read back");
+        read_back(last, "a chain's last buffer does not read back");
+        break;
+      }
+      case 0: case 1: queue_traversal(3 + rnd(14)); break;                       // a long list
+      case 2: queue_traversal(1 + rnd(2)); break;                                // a short one
+      case 3:
+      { // an evaluation
+        EdgeEval ee{any_child(-1), any_child(-1), rnd(I->nmat), nullptr, true, nullptr};
+        M.launch(&ee);
+        break;
+      }
+      case 4: M.launch(nullptr); break;                                          // a launch without an evaluation
+      case 5:
+      { // a reader of memory (phyhip_get_partials, Update_Eigen_Lr as its own kernel): the buffer is stored after the launch
+        const int b = tips + rnd(I->nbuf - tips);
+        if (!M.written[b]) break;
+        reader(b);
+        M.launch(nullptr);
+        read_back(b, "a reader finds its buffer unstored or stale");
+        break;
+      }
+      case 6:
+      { // a matrix changes (store-first route): what is queued runs on the old value, dependants are stored on it
+        const int m = rnd(I->nmat);
+        M.launch(nullptr);
+        devirtualise_matrix(I, m);
+        M.launch(nullptr);
+        for (int b = tips; b < I->nbuf; ++b)
+          if (is_unstored(I, b) && (unstored_def(I, b).pm1 == m || unstored_def(I, b).pm2 == m))
+            M.die("an unstored buffer still reads a matrix that changes", b, m);
+        ++M.matv[m];
+        break;
+      }
+      case 7:
+      { // a tip row changes
+        const int t = rnd(tips);
+        M.launch(nullptr);
+        devirtualise_tip(I, t);
+        M.launch(nullptr);
+        for (int b = tips; b < I->nbuf; ++b)
+          if (is_unstored(I, b) && (unstored_def(I, b).c1 == t || unstored_def(I, b).c2 == t))
+            M.die("an unstored buffer still reads a tip row that changes", b, t);
+        ++M.tipv[t];
+        break;
+      }
+      case 8:
+        if (rnd(4) == 0)
+        { // everything stored (phyhip_set_virtual_buffers(0) / another threshold)
+          I->virt_min_ops = 0;
+          devirtualise_all(I);
+          M.launch(nullptr);
+          if (n_unstored(I) != 0) M.die("devirtualise_all left unstored buffers");
+          I->virt_min_ops = 1 + rnd(12);
+          I->chain_min_ops = rnd(5) ? 3 + rnd(10) : 0; // (the chained class has its own threshold; 0: off, what is chained stays until settled)
+        }
+        break;
+      default: queue_traversal(6 + rnd(20)); break;
+    }
+  }
+  M.launch(nullptr);
+  printf("VIRT_CHAIN_MODEL OK seed %u: %ld launches, %llu stores skipped, %ld in-step children, %ld non-storing operations, %llu stored on demand, %ld odd lists re-ran their last operation, %llu stores deferred, %llu deferred stored on demand, %llu deferred dropped, %ld input writes, %ld replays, %llu stores chained, %llu chained stored on demand, %llu chained dropped, %ld longest chain, %ld writes under a chained input, %ld reads of chain ends, %ld queues rewritten twice\n",
+         seed, M.n_launch, (unsigned long long)I->n_virt_skipped, M.n_instep, M.n_nostore, (unsigned long long)I->n_virt_material, M.n_pad,
+         (unsigned long long)I->n_def_skipped, (unsigned long long)I->n_def_material, (unsigned long long)I->n_def_dropped, n_input_writes, n_replays,
+         (unsigned long long)I->n_chain_skipped, (unsigned long long)I->n_chain_material, (unsigned long long)I->n_chain_dropped, M.max_chain, n_mid_writes, n_end_reads, n_double);
+  return 0;
+}
