@@ -364,17 +364,11 @@ static int build_instance(Instance *I, const hipDeviceProp_t &prop)
   // ... and devirtualise() puts up to one storing definition per internal buffer in front of the queue: 3 x (queue + internal
   // buffers) records bound every rewritten list (flush_impl refuses a longer one instead of overrunning the slot)
   I->ops_slot_bytes = (size_t)(3 * (I->ops_cap + (I->nbuf - I->tips)) + 2) * (sizeof(IssueRec) + sizeof(ExecRec));
-  I->virt.assign(I->nbuf, 0);
-  I->keep_real_flag.assign(I->nbuf, 0);
-  I->vdef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
+  I->unstored.resize(I->nbuf);
   // (deferred buffers need what virtual ones need: the two snapshot slots per internal buffer, the kernels with two-deep forwarding)
-  I->deferred.assign(I->nbuf, 0);
-  I->ddef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
-  I->defer_stores = I->nmat_all >= I->nmat + 2 * (I->nbuf - I->tips) && I->nbuf > I->tips;
+  I->unstored.defer_stores = I->nmat_all >= I->nmat + 2 * (I->nbuf - I->tips) && I->nbuf > I->tips;
   // (chained buffers: the third class, on top of the deferred one -- one-sided lists of at least chain_min_ops operations)
-  I->chained.assign(I->nbuf, 0);
-  I->def_seq.assign(I->nbuf, 0);
-  I->chain_min_ops = I->defer_stores ? 16 : 0;
+  I->unstored.chain_min_ops = I->unstored.defer_stores ? 16 : 0;
   HIPCHK(hipMalloc((void **)&I->d_ops, (size_t)I->ops_slots * I->ops_slot_bytes));
   size_t chunk = std::max<size_t>(64 * 1024, std::max(I->ops_slot_bytes,
                                                        (size_t)I->C * I->S * I->S * sizeof(double) * 4));
@@ -387,7 +381,7 @@ static int build_instance(Instance *I, const hipDeviceProp_t &prop)
   I->slot_ops.assign(I->ops_slots, std::vector<DevOp>());
   I->slot_inl.assign(I->ops_slots, std::vector<InlineDef>());
   if (const char *e = diag_env("PHYHIP_VIRT_INLINE")) I->virt_inline = atoi(e) != 0;
-  if (const char *e = diag_env("PHYHIP_VIRT_MIN_OPS")) I->virt_min_ops = std::max(0, atoi(e)); // (diag: phyhip_set_virtual_buffers' threshold from the environment)
+  if (const char *e = diag_env("PHYHIP_VIRT_MIN_OPS")) I->unstored.virt_min_ops = std::max(0, atoi(e)); // (diag: phyhip_set_virtual_buffers' threshold from the environment)
   I->slot_kind.assign(I->ops_slots, -1);
   if (const char *e = diag_env("PHYHIP_GENERIC_NT")) I->generic_nt = atoi(e) != 0;
   if (I->generic_loop) I->generic_nt = true;
@@ -755,10 +749,10 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
   for (int i = 0; i < count && !queued_reader; ++i) queued_reader = I->mat_in_queue[idx[i]] != 0;
   // does an unstored buffer's definition -- virtual, deferred or chained -- read one of them?  (a scan of the buffer flags: only while there are some)
   auto depends = [&]() {
-    for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
-      if (is_unstored(I, b))
+    for (int b = I->tips; b < I->nbuf && I->unstored.n_unstored() > 0; ++b)
+      if (I->unstored.is_unstored(b))
       {
-        const DevOp &d = unstored_def(I, b);
+        const DevOp &d = I->unstored.def(b);
         for (int i = 0; i < count; ++i)
           if (d.pm1 == idx[i] || d.pm2 == idx[i]) return true;
       }
@@ -772,8 +766,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     int rc = flush(I, nullptr);
     if (rc) return rc;
   }
-  if (n_unstored(I) == 0) return 0;
-  const unsigned long long stored_before = I->n_virt_material + I->n_def_material + I->n_chain_material;
+  if (I->unstored.n_unstored() == 0) return 0;
+  const unsigned long long stored_before = I->unstored.n_material();
   // A virtual buffer is defined on the matrices as they are.  Before one changes: pmat_kernel / upload_matrices_kernel move the
   // old value into the buffer's own snapshot slot, and the definition reads it there from now on (a full traversal that follows
   // recomputes every buffer anyway; the host route rewrites a tree's matrices one call at a time) -- or the buffer is stored first.
@@ -792,10 +786,10 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
         if (idx[i] == pm) return i;
       return -1;
     };
-    for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
+    for (int b = I->tips; b < I->nbuf && I->unstored.n_unstored() > 0; ++b)
     {
-      if (!is_unstored(I, b)) continue;
-      DevOp &d = unstored_def(I, b); // (a deferred or chained buffer's two snapshot slots are its own as well)
+      if (!I->unstored.is_unstored(b)) continue;
+      DevOp &d = I->unstored.def(b); // (a deferred or chained buffer's two snapshot slots are its own as well)
       const int  i1 = pos(d.pm1), i2 = pos(d.pm2);
       if (i1 < 0 && i2 < 0) continue;
       if (shadow->empty()) shadow->assign(count, -1);
@@ -808,8 +802,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
     }
   }
   else
-    for (int i = 0; i < count && n_unstored(I) > 0; ++i) devirtualise_matrix(I, idx[i]);
-  if (I->n_virt_material + I->n_def_material + I->n_chain_material != stored_before)
+    for (int i = 0; i < count && I->unstored.n_unstored() > 0; ++i) devirtualise_matrix(I, idx[i]);
+  if (I->unstored.n_material() != stored_before)
   { // (stored on the old values: now)
     int rc = flush(I, nullptr);
     if (rc) return rc;
@@ -1322,8 +1316,8 @@ int phyhip_set_virtual_buffers(int instance, int minOperations)
   if (Group *G = get_group(instance)) return group_each(G, [&](int id, long long, long long) { return phyhip_set_virtual_buffers(id, minOperations); });
   GET_INST(I, instance);
   if (minOperations < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "minOperations %d", minOperations);
-  I->virt_min_ops = minOperations;
-  if (minOperations == 0 && n_unstored(I) > 0)
+  I->unstored.virt_min_ops = minOperations;
+  if (minOperations == 0 && I->unstored.n_unstored() > 0)
   {
     devirtualise_all(I);
     return flush(I, nullptr);
@@ -1336,7 +1330,8 @@ int phyhip_get_virtual_stats(int instance, long long out[4])
   if (Group *G = get_group(instance)) return phyhip_get_virtual_stats(G->sub_id[0], out);
   GET_INST_RES(I, instance);
   I_call.leave_query();
-  out[0] = I->n_virtual; out[1] = (long long)I->n_virt_skipped; out[2] = (long long)I->n_virt_recomputed; out[3] = (long long)I->n_virt_material;
+  const Unstored::Counters &c = I->unstored.counters(Unstored::kVirtual);
+  out[0] = I->unstored.n(Unstored::kVirtual); out[1] = (long long)c.skipped; out[2] = (long long)I->unstored.n_recomputed; out[3] = (long long)c.material;
   return PHYHIP_SUCCESS;
 }
 
@@ -1344,7 +1339,8 @@ int phyhip_get_deferred_stats(int instance, long long out[4])
 {
   if (Group *G = get_group(instance)) return phyhip_get_deferred_stats(G->sub_id[0], out);
   GET_INST(I, instance); // (an ordinary entry: the resident-aware queries are a reviewed list, tests/test_abi.py)
-  out[0] = I->n_deferred; out[1] = (long long)I->n_def_skipped; out[2] = (long long)I->n_def_material; out[3] = (long long)I->n_def_dropped;
+  const Unstored::Counters &c = I->unstored.counters(Unstored::kDeferred);
+  out[0] = I->unstored.n(Unstored::kDeferred); out[1] = (long long)c.skipped; out[2] = (long long)c.material; out[3] = (long long)c.dropped;
   return PHYHIP_SUCCESS;
 }
 
@@ -1353,7 +1349,7 @@ int phyhip_set_chained_buffers(int instance, int minOperations)
   if (Group *G = get_group(instance)) return group_each(G, [&](int id, long long, long long) { return phyhip_set_chained_buffers(id, minOperations); });
   GET_INST(I, instance);
   if (minOperations < 0) return fail(PHYHIP_ERROR_OUT_OF_RANGE, "minOperations %d", minOperations);
-  I->chain_min_ops = I->defer_stores ? minOperations : 0; // (what is chained now stays so until something needs it: the next list settles it)
+  I->unstored.chain_min_ops = I->unstored.defer_stores ? minOperations : 0; // (what is chained now stays so until something needs it: the next list settles it)
   return PHYHIP_SUCCESS;
 }
 
@@ -1361,7 +1357,8 @@ int phyhip_get_chained_stats(int instance, long long out[4])
 {
   if (Group *G = get_group(instance)) return phyhip_get_chained_stats(G->sub_id[0], out);
   GET_INST(I, instance);
-  out[0] = I->n_chained; out[1] = (long long)I->n_chain_skipped; out[2] = (long long)I->n_chain_material; out[3] = (long long)I->n_chain_dropped;
+  const Unstored::Counters &c = I->unstored.counters(Unstored::kChained);
+  out[0] = I->unstored.n(Unstored::kChained); out[1] = (long long)c.skipped; out[2] = (long long)c.material; out[3] = (long long)c.dropped;
   return PHYHIP_SUCCESS;
 }
 

@@ -3,6 +3,8 @@
 //   phyhip.hip           the C ABI: life cycle, inputs, transition matrices, the queueing entry points, getters, plumbing
 //   phyhip_queue.hip     the deferred queue turned into launches or resident commands (flush_impl and its stages),
 //                        the waits for their scalars
+//   phyhip_unstored.hip  which results a launch leaves unstored (virtual, deferred, chained: Unstored below), what is stored in front
+//                        of a queue that needs them, the queue as it will be launched (rewrite_pending, devirtualise*); host code only
 //   phyhip_resident.hip  host side of the resident evaluators (small and large-grid)
 //   phyhip_eigen.hip     Update_Eigen_Lr / dLk entry points
 //   phyhip_mixture.hip   mixtures (class instances, class axis)
@@ -190,6 +192,79 @@ struct InlineDef
   bool operator==(const InlineDef &o) const { return a == o.a && b == o.b && pmA == o.pmA && pmB == o.pmB; }
 };
 
+// The buffers a launch leaves UNSTORED: per buffer its class, the operation that computes it and the number of
+// that definition; per class the count and the counters; and every transition in one place (make / renew / end), so that no caller
+// touches a class and a counter separately.  Who decides what: phyhip_unstored.hip.
+//   virtual   a whole-tree traversal does not STORE the results of its tip x tip operations -- each is recomputed in registers
+//             right in front of the operation that consumes it (two matrix columns and a product per pattern: cheaper than the
+//             16-byte-per-entry write and the read back) -- so the buffer's memory is stale until something needs it: then the
+//             defining operation is queued again, storing (devirtualise).  The tips and the two matrices the definition reads may
+//             not change while it stands (matrices_touch, the tip setters).
+//   deferred  a result every reader takes from registers, one step over inputs the launch leaves in memory (defer_forwarded).
+//             Whatever stores a virtual buffer stores a deferred one; a later list settles it (settle_deferred).
+//   chained   the same in a one-sided list of at least chain_min_ops operations, over inputs that may be unstored themselves
+//             (defer_forwarded's second pass).  So definitions are ordered: each, of any class, carries a number from one counter,
+//             an input's lower than its dependant's; whatever stores a chained buffer stores its unstored inputs in front of it,
+//             and the definitions in front of `pending` (the first n_front entries) stand in ascending order of these numbers.
+struct Unstored
+{
+  enum Class : unsigned char { kStored = 0, kVirtual, kDeferred, kChained };
+  // how a definition ends: stored on demand (the class's `material` counter), dropped because a list writes the buffer first
+  // (`dropped`), overwritten by a storing operation of the list that is being rewritten, written by a short launch (no counter)
+  enum End { kMaterial, kDropped, kOverwritten, kShortLaunch };
+  struct Counters { unsigned long long skipped = 0, material = 0, dropped = 0; }; // phyhip_get_{virtual,deferred,chained}_stats
+
+  int  virt_min_ops  = 16;    // lists at least this long leave tip x tip results virtual (0: never, and no other class either)
+  bool defer_stores  = false; // the deferred class (phyhip_create_instance: on where the snapshot slots exist)
+  int  chain_min_ops = 0;     // lists at least this long chain (0: never); phyhip_create_instance: 16
+  int  n_front       = 0;     // stored definitions at the head of `pending` (until it is launched: retire_queue, or rewritten as a long list)
+  unsigned long long n_recomputed = 0; // virtual children computed in-step or re-issued (phyhip_get_virtual_stats)
+  std::vector<int>   keep_real;        // buffers the caller reads from MEMORY right after the next launch (devirtualise): that launch leaves them stored
+
+  void resize(int nbuf) { cls_.assign(nbuf, kStored); kept_.assign(nbuf, 0); seq_.assign(nbuf, 0); def_.assign(nbuf, DevOp{0, 0, 0, 0, 0, 0}); }
+  bool  is_unstored(int b) const { return cls_[b] != kStored; }
+  Class class_of(int b) const { return (Class)cls_[b]; }
+  DevOp &def(int b) { return def_[b]; } // (the matrix setters move a definition's matrices to the buffer's snapshot slots)
+  const DevOp &def(int b) const { return def_[b]; }
+  unsigned long long seq(int b) const { return seq_[b]; }
+  int n(Class c) const { return n_[c]; }
+  int n_unstored() const { return n_[kVirtual] + n_[kDeferred] + n_[kChained]; }
+  const Counters &counters(Class c) const { return cnt_[c]; }
+  unsigned long long n_material() const { return cnt_[kVirtual].material + cnt_[kDeferred].material + cnt_[kChained].material; }
+
+  // buffer b, stored until now, is what `op` says from here on: unstored in class c, under the newest number
+  void make(Class c, int b, const DevOp &op)
+  {
+    cls_[b] = c; def_[b] = op; def_[b].pad = 0;
+    ++n_[c]; ++cnt_[c].skipped;
+    renew(b);
+  }
+  void renew(int b) { seq_[b] = ++next_seq_; } // (defer_forwarded: a deferred definition whose input the same list chains behind it)
+  void end(int b, End why)
+  {
+    Counters &c = cnt_[cls_[b]];
+    --n_[cls_[b]]; cls_[b] = kStored;
+    c.material += why == kMaterial; c.dropped += why == kDropped;
+  }
+  // (a flag per buffer + the list of the flagged ones: constant-time lookup in rewrite_pending, no duplicates; cleared once the
+  // launch in between has happened: nothing is asked to stay stored any more)
+  bool kept(int b) const { return kept_[b] != 0; }
+  void keep(int b) { if (!kept_[b]) { kept_[b] = 1; keep_real.push_back(b); } }
+  void keep_clear()
+  {
+    for (int b : keep_real) kept_[b] = 0;
+    keep_real.clear();
+  }
+
+ private:
+  std::vector<unsigned char>      cls_, kept_; // [nbuf]
+  std::vector<DevOp>              def_;        // [nbuf]
+  std::vector<unsigned long long> seq_;        // [nbuf]
+  unsigned long long              next_seq_ = 0;
+  int                             n_[4]     = {0, 0, 0, 0}; // live definitions per class
+  Counters                        cnt_[4];
+};
+
 struct Instance
 {
   Collective *co         = nullptr; // one-process-per-GPU mode: communicator attached by phyhip_comm_init_rank
@@ -304,46 +379,10 @@ struct Instance
   int       grid = 0, grid_nt = 0, block_nt = 64;
 
   std::vector<DevOp>                     pending;
-  // Virtual buffers: a whole-tree traversal does not STORE the results of its tip x tip operations -- each
-  // is recomputed in registers right in front of the operation that consumes it (two matrix columns and a product per
-  // pattern: cheaper than the 16-byte-per-entry write and the read back) -- so the buffer's memory is stale until something
-  // needs it: then the defining operation is queued again, storing (devirtualise).  virt[b] != 0 says so, vdef[b] is that
-  // operation; the tips and the two matrices it reads may not change while virt[b] (matrices_touch, the tip setters).
-  int                                    virt_min_ops = 16; // lists at least this long leave tip x tip results virtual (0: never)
-  int                                    n_virtual = 0;
+  Unstored                               unstored;           // which buffers the launches left unstored, and how to compute them (above)
   bool                                   virt_inline = true; // (diag: PHYHIP_VIRT_INLINE=0 re-issues every virtual child as a step of its own)
   std::vector<InlineDef>                 pending_inl;        // per entry of `pending` as rewrite_pending left it (or empty: none has one)
   std::vector<std::vector<InlineDef>>    slot_inl;           // ... of the lists the device ring slots hold (content cache)
-  std::vector<unsigned char>             virt;              // [nbuf]
-  std::vector<DevOp>                     vdef;              // [nbuf]
-  std::vector<unsigned char>             keep_real_flag;    // [nbuf]: buffer is in keep_real
-  std::vector<int>                       keep_real;         // buffers the caller reads from MEMORY right after the next launch (devirtualise): that launch leaves them stored
-  unsigned long long                     n_virt_skipped = 0, n_virt_recomputed = 0, n_virt_material = 0; // phyhip_get_virtual_stats
-  // Deferred buffers: the second class of unstored buffer.  A long list does not store a result that every
-  // reader in it takes from registers (the previous two operations') when its children are tips or buffers the launch leaves in
-  // memory: deferred[b] != 0, ddef[b] is the operation (one step over stored inputs, pad 0).  Whatever stores a virtual buffer
-  // stores a deferred one (devirtualise*); a later list that writes the buffer first drops the definition, one that reads it first
-  // or writes one of its inputs stores it in front (rewrite_pending).  Off in a hand-built Instance: phyhip_create_instance
-  // switches it on and sizes the vectors, and nothing indexes them before.
-  bool                                   defer_stores = false;
-  int                                    n_deferred = 0;
-  std::vector<unsigned char>             deferred;          // [nbuf]
-  std::vector<DevOp>                     ddef;              // [nbuf]
-  unsigned long long                     n_def_skipped = 0, n_def_material = 0, n_def_dropped = 0; // phyhip_get_deferred_stats
-  // Chained buffers: the third class.  A one-sided list of at least chain_min_ops operations -- one in which no
-  // transition matrix is read twice -- leaves a forwarded result unstored also when a child is itself unstored after the launch
-  // (virtual, deferred, or chained earlier in the list): chained[b] != 0, the operation is in ddef[b] (a buffer is deferred or
-  // chained, never both).  Such definitions are ordered: every definition of any class carries a number from one counter
-  // (def_seq[b], from next_seq), so an input's is lower than its dependant's, and whatever stores a chained buffer stores its
-  // unstored inputs in front of it, transitively; the definitions standing in front of `pending` (the first n_front entries) are
-  // kept in ascending order of these numbers.  Off (chain_min_ops == 0, def_seq empty) in a hand-built Instance.
-  int                                    chain_min_ops = 0; // lists at least this long chain (0: never); phyhip_create_instance: 16
-  int                                    n_chained = 0;
-  int                                    n_front = 0;       // stored definitions at the head of `pending` (until it is launched: retire_queue, or rewritten as a long list)
-  std::vector<unsigned char>             chained;           // [nbuf]
-  std::vector<unsigned long long>        def_seq;           // [nbuf]
-  unsigned long long                     next_seq = 0;
-  unsigned long long                     n_chain_skipped = 0, n_chain_material = 0, n_chain_dropped = 0; // phyhip_get_chained_stats
   std::vector<int>                       pm_idx;    // queued device-side matrix rebuilds (index, edge length)
   std::vector<double>                    pm_len;
   std::vector<int>                       pm_slot;   // matrix index -> position in pm_idx, or -1
@@ -601,26 +640,17 @@ int  check_partial_index(const Instance *I, int idx, bool allow_tip);
 int  wait_host_sum(Instance *I);
 int  wait_result(Instance *I);
 int  collect_profile(Instance *I);
-void devirtualise(Instance *I, int buf);       // queue (in front) the storing operation that makes buffer `buf` real again, behind those of its unstored inputs
+
+// ---- phyhip_unstored.hip ---------------------------------------------------------------------------------------------------
+constexpr int kOpNoStore = 1; // DevOp::pad bit 0: the operation's result is forwarded in registers only (descriptors of size 0)
+constexpr int kOpInl1 = 2, kOpInl2 = 4; // DevOp::pad bits 1, 2: child 1 / child 2 is computed inside the operation's own step (Instance::pending_inl)
+void devirtualise(Instance *I, int buf);     // queue (in front) the storing operation that makes buffer `buf` real again, behind those of its unstored inputs
 void devirtualise_all(Instance *I);
 void devirtualise_matrix(Instance *I, int m);  // ... for every virtual buffer whose definition reads matrix m
 void devirtualise_tip(Instance *I, int tip);   // ... reads tip row `tip`
 void devirtualise_dependants(Instance *I, int buf); // ... for every deferred or chained buffer whose definition reads buffer `buf` (about to be written outside the queue)
 // snapshot slot w (0: the definition's first matrix, 1: its second) of internal buffer b in the matrix tables
-// (the launch in between has happened: nothing is asked to stay stored any more)
-inline void keep_real_clear(Instance *I)
-{
-  for (int b : I->keep_real) I->keep_real_flag[b] = 0;
-  I->keep_real.clear();
-}
 inline int shadow_slot(const Instance *I, int b, int w) { return I->nmat + 2 * (b - I->tips) + w; }
-// the three classes of unstored buffer: virtual, deferred, chained -- and the definition of one (vdef, or ddef for the other two)
-inline int  n_unstored(const Instance *I) { return I->n_virtual + I->n_deferred + I->n_chained; }
-inline bool is_unstored(const Instance *I, int b)
-{
-  return I->virt[b] || (I->n_deferred > 0 && I->deferred[b]) || (I->n_chained > 0 && I->chained[b]);
-}
-inline DevOp &unstored_def(Instance *I, int b) { return I->virt[b] ? I->vdef[b] : I->ddef[b]; }
 void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise);
 
 // ---- resident evaluators: host side -----------------------------------------------------------------------------

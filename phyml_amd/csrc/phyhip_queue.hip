@@ -6,356 +6,6 @@
 namespace phyhip_host
 {
 
-// ---- virtual buffers (Instance::virt) ---------------------------------------------------------------------------------------
-constexpr int kOpNoStore = 1; // DevOp::pad bit 0: the operation's result is forwarded in registers only (descriptors of size 0)
-constexpr int kOpInl1 = 2, kOpInl2 = 4; // DevOp::pad bits 1, 2: child 1 / child 2 is computed inside the operation's own step (Instance::pending_inl)
-
-// The launch in between must leave the buffer in memory, whatever the queue does with it (rewrite_pending)
-static void keep_stored(Instance *I, int buf)
-{
-  if (buf >= I->tips && buf < I->nbuf && I->virt_min_ops > 0 && !I->keep_real_flag[buf])
-  { // (a flag per buffer + the list of the flagged ones: constant-time lookup in rewrite_pending, no duplicates)
-    I->keep_real_flag[buf] = 1;
-    I->keep_real.push_back(buf);
-  }
-}
-
-// The storing definition of one unstored buffer into the front of the queue.  A virtual definition reads tips, a deferred one
-// tips and buffers that have not been written since (rewrite_pending stores or drops it before one is); such a buffer may be
-// unstored itself -- under a chained definition, and under a deferred one made by a list that chains (defer_forwarded's second pass) -- and then
-// its definition goes in first, transitively.  With sequence numbers (Instance::def_seq) the definitions in front of the queue
-// stay in ascending order, so one queued by an earlier call that reads a buffer stored by this one still finds it written in
-// front of it; without them (a hand-built Instance, no chained class) each goes to the very front.
-static void store_definition(Instance *I, int buf)
-{
-  const bool v = I->virt[buf] != 0, ch = !v && I->n_chained > 0 && I->chained[buf];
-  DevOp      op = v ? I->vdef[buf] : I->ddef[buf];
-  op.pad = 0;
-  if (!v && I->n_chained > 0) // (a deferred definition's inputs were stored when it was made; a list that chains may have left one unstored behind it)
-    for (int c : {op.c1, op.c2})
-      if (c >= I->tips && is_unstored(I, c))
-      { // (stored for good, like the buffer that was asked for: whoever asked may be about to change a tip row or a matrix under it)
-        keep_stored(I, c);
-        store_definition(I, c);
-      }
-  size_t at = 0;
-  if (!I->def_seq.empty())
-  {
-    I->n_front = std::min(I->n_front, (int)I->pending.size());
-    while (at < (size_t)I->n_front && I->def_seq[I->pending[at].dest] < I->def_seq[buf]) ++at;
-    ++I->n_front;
-  }
-  I->pending.insert(I->pending.begin() + (long)at, op);
-  I->mat_in_queue[op.pm1] = 1; I->mat_in_queue[op.pm2] = 1;
-  if (v) { I->virt[buf] = 0; --I->n_virtual; ++I->n_virt_material; }
-  else if (ch) { I->chained[buf] = 0; --I->n_chained; ++I->n_chain_material; }
-  else { I->deferred[buf] = 0; --I->n_deferred; ++I->n_def_material; }
-}
-
-void devirtualise(Instance *I, int buf)
-{
-  // whoever asks is about to read the buffer from memory -- a kernel outside the traversal launch (eigen_lr_kernel, a mixture
-  // combination), a copy to the host, or a setter that changes what the buffer was computed from: the launch in between must not
-  // leave it virtual AGAIN (a long queue that writes it with a tip x tip operation and reads it later would: rewrite_pending)
-  keep_stored(I, buf);
-  if (buf < I->tips || buf >= I->nbuf || !is_unstored(I, buf)) return;
-  store_definition(I, buf);
-}
-
-void devirtualise_all(Instance *I)
-{
-  for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
-    if (is_unstored(I, b)) devirtualise(I, b);
-}
-
-void devirtualise_matrix(Instance *I, int m)
-{
-  for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
-    if (is_unstored(I, b) && (unstored_def(I, b).pm1 == m || unstored_def(I, b).pm2 == m)) devirtualise(I, b);
-}
-
-void devirtualise_tip(Instance *I, int tip)
-{
-  for (int b = I->tips; b < I->nbuf && n_unstored(I) > 0; ++b)
-    if (is_unstored(I, b) && (unstored_def(I, b).c1 == tip || unstored_def(I, b).c2 == tip)) devirtualise(I, b);
-}
-
-// A buffer is about to be written by something that does not pass through the queue (a setter): deferred and chained buffers whose
-// definitions read it are stored first, on its old value (their own dependants then read them from memory)
-void devirtualise_dependants(Instance *I, int buf)
-{
-  if (buf < I->tips) return;
-  for (int b = I->tips; b < I->nbuf && I->n_deferred + I->n_chained > 0; ++b)
-    if (!I->virt[b] && is_unstored(I, b) && (I->ddef[b].c1 == buf || I->ddef[b].c2 == buf)) devirtualise(I, b);
-}
-
-// settle_deferred with chained definitions about: one rule for the deferred and the chained class.  For the definition d of b --
-// needed: b is read before it is written; dead: b is written before it is read.  M0 = {needed} + {not dead, and the list writes
-// one of d's input buffers}; M = M0 closed under "unstored input of a member" (store_definition's recursion).  M is stored in
-// front, in sequence order; dead definitions outside M are dropped; the rest stays.  A kept definition cannot have a dropped
-// input: the list writes that input, which puts the dependant into M0.  (A dead input in M is stored and overwritten later.)
-static bool settle_chained(Instance *I, const std::vector<int> &first_read, const std::vector<int> &first_write, int never)
-{
-  auto written = [&](int c) { return c >= I->tips && first_write[c] != never; };
-  const unsigned long long before = I->n_virt_material + I->n_def_material + I->n_chain_material;
-  std::vector<int> m0;
-  for (int b = I->tips; b < I->nbuf; ++b)
-  {
-    if (I->virt[b] || !is_unstored(I, b)) continue;
-    const bool needed = first_read[b] < first_write[b], dead = !needed && first_write[b] != never;
-    if (needed || (!dead && (written(I->ddef[b].c1) || written(I->ddef[b].c2)))) m0.push_back(b);
-  }
-  for (int b : m0)
-    if (is_unstored(I, b)) devirtualise(I, b); // (an earlier member's closure may have stored it)
-  for (int b = I->tips; b < I->nbuf && I->n_deferred + I->n_chained > 0; ++b)
-  {
-    if (I->virt[b] || !is_unstored(I, b) || first_write[b] == never) continue; // (what is still flagged is not needed: dead)
-    if (I->deferred[b]) { I->deferred[b] = 0; --I->n_deferred; ++I->n_def_dropped; }
-    else { I->chained[b] = 0; --I->n_chained; ++I->n_chain_dropped; }
-  }
-  return I->n_virt_material + I->n_def_material + I->n_chain_material != before;
-}
-
-// Deferred buffers left by earlier launches against the list that is about to run and its evaluation, in order.  The list reads
-// the buffer before it writes it: stored in front.  It writes the buffer first: the old definition is dead (every repeated
-// whole-tree traversal ends here for every deferred buffer: two scans of the list, nothing launched).  It does not write the buffer
-// but one of its inputs: stored in front, where the definition still reads the input's old value.  Returns whether it stored one
-// (a short launch then stores them all: it is a list now in any case, and the short launches behind it keep their form).
-static bool settle_deferred(Instance *I, const EdgeEval *ee)
-{
-  if (I->n_deferred == 0 && I->n_chained == 0) return false;
-  const int        n0 = (int)I->pending.size(), never = n0 + 1;
-  std::vector<int> first_read(I->nbuf, never), first_write(I->nbuf, never);
-  // (chained definitions about: the stored definitions already standing in front write values their dependants are defined on --
-  // making an input real does not invalidate a dependant)
-  for (int k = I->n_chained > 0 ? std::min(I->n_front, n0) : 0; k < n0; ++k)
-  {
-    const DevOp &o = I->pending[k];
-    for (int c : {o.c1, o.c2})
-      if (c >= I->tips && first_read[c] == never) first_read[c] = k;
-    if (first_write[o.dest] == never) first_write[o.dest] = k;
-  }
-  if (ee)
-    for (int c : {ee->parent, ee->child})
-      if (c >= I->tips && first_read[c] == never) first_read[c] = n0;
-  if (I->n_chained > 0) return settle_chained(I, first_read, first_write, never);
-  bool stored = false;
-  auto written = [&](int c) { return c >= I->tips && first_write[c] != never; };
-  for (int b = I->tips; b < I->nbuf && I->n_deferred > 0; ++b)
-  {
-    if (!I->deferred[b]) continue;
-    if (first_read[b] < first_write[b]) { stored = true; devirtualise(I, b); }
-    else if (first_write[b] != never) { I->deferred[b] = 0; --I->n_deferred; ++I->n_def_dropped; }
-    else if (written(I->ddef[b].c1) || written(I->ddef[b].c2)) { stored = true; devirtualise(I, b); } // (an input is written)
-  }
-  return stored;
-}
-
-// (every definition of an unstored buffer, of any class, in the order they are made: Instance::def_seq)
-static inline void stamp_definition(Instance *I, int b)
-{
-  if (!I->def_seq.empty()) I->def_seq[b] = ++I->next_seq;
-}
-
-// Does the list qualify for the chained class?  At least chain_min_ops operations, virtual buffers on, and no transition matrix
-// read twice (one-sided traversals: in a both-sided one the post-order and the pre-order share the edge matrices, and each refresh
-// of one would store whole closures -- matrices_touch).
-static bool list_chains(const Instance *I, const std::vector<DevOp> &L, const std::vector<InlineDef> &LI)
-{
-  const int n = (int)L.size();
-  if (I->chain_min_ops <= 0 || n < I->chain_min_ops || I->virt_min_ops <= 0 || I->chained.empty()) return false;
-  std::vector<unsigned char> seen(I->mat_in_queue.size(), 0);
-  auto twice = [&](int m) { if (m < 0) return false; if (seen[m]) return true; seen[m] = 1; return false; };
-  for (int k = 0; k < n; ++k)
-  {
-    if (twice(L[k].pm1) || twice(L[k].pm2)) return false;
-    if ((L[k].pad & (kOpInl1 | kOpInl2)) && (twice(LI[k].pmA) || twice(LI[k].pmB))) return false;
-  }
-  return true;
-}
-
-// Deferred buffers, the rule (on the list as it will be launched, front to back): a storing operation whose destination is written
-// once in the list, read in it only by the next two operations -- exactly the reads child_descs forwards in registers -- and
-// neither read by the evaluation nor asked for from memory (keep_real) does not store, if each child is a tip or a buffer that is
-// in memory after this launch: not virtual, not computed in-step, not deferred, not written again behind the operation.  So every
-// deferred definition is made as ONE step over stored inputs, and in a list that does not chain it stays so: no recursion and no
-// order among definitions.
-// Chained buffers (`chain`: list_chains), a second pass with the same conditions over what the first left storing, but for the
-// children: a child may be a tip or ANY buffer that is not written again behind the operation.  It is then either in memory
-// after this launch, or unstored under a definition that computes the value this operation read -- virtual (read in-step or
-// through a re-issue; a list writes a buffer it leaves virtual once), deferred, or chained earlier in this list.  In such a list a
-// result deferred by the first pass may see one of its stored inputs chained by the second (it is one of that input's two readers):
-// then the deferred definition reads an unstored buffer too, and its sequence number is renewed so that the definitions of the
-// list are numbered in list order, inputs before dependants (store_definition follows the inputs of both classes).
-static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> &L, bool chain)
-{
-  const int        n = (int)L.size();
-  std::vector<int> n_dest(I->nbuf, 0), last_write(I->nbuf, -1), last_read(I->nbuf, -1);
-  for (int k = 0; k < n; ++k)
-  {
-    const DevOp &o = L[k];
-    ++n_dest[o.dest];
-    last_write[o.dest] = k;
-    if (o.c1 >= I->tips && !(o.pad & kOpInl1)) last_read[o.c1] = k;
-    if (o.c2 >= I->tips && !(o.pad & kOpInl2)) last_read[o.c2] = k;
-  }
-  // (the padded re-run of an odd list's last operation: the result three positions back is no longer in registers)
-  const int pad_read1 = (n & 1) ? L[n - 1].c1 : -1, pad_read2 = (n & 1) ? L[n - 1].c2 : -1;
-  auto in_memory = [&](int c, bool in_step, int i) {
-    return c < I->tips || (!in_step && !I->virt[c] && !I->deferred[c] && last_write[c] < i);
-  };
-  auto not_rewritten = [&](int c, int i) { return c < I->tips || last_write[c] < i; };
-  for (int pass = 0; pass < (chain ? 2 : 1); ++pass)
-    for (int i = 0; i + 1 < n; ++i)
-    {
-      DevOp &o = L[i];
-      if (pass == 1 && (o.pad & kOpNoStore) && !I->virt[o.dest] && I->deferred[o.dest]) stamp_definition(I, o.dest); // (deferred by pass 0)
-      if ((o.pad & kOpNoStore) || n_dest[o.dest] != 1) continue;
-      if (last_read[o.dest] <= i || last_read[o.dest] > i + 2) continue; // (never read behind it, or read from memory)
-      if ((ee && (ee->parent == o.dest || ee->child == o.dest)) || I->keep_real_flag[o.dest]) continue;
-      if (pass == 0 && (!in_memory(o.c1, o.pad & kOpInl1, i) || !in_memory(o.c2, o.pad & kOpInl2, i))) continue;
-      if (pass == 1 && (!not_rewritten(o.c1, i) || !not_rewritten(o.c2, i))) continue;
-      if (i + 3 == n && (pad_read1 == o.dest || pad_read2 == o.dest)) continue; // (the odd-list rule, for this class)
-      I->ddef[o.dest] = o;
-      I->ddef[o.dest].pad = 0;
-      if (pass == 0) { I->deferred[o.dest] = 1; ++I->n_deferred; ++I->n_def_skipped; }
-      else { I->chained[o.dest] = 1; ++I->n_chained; ++I->n_chain_skipped; }
-      stamp_definition(I, o.dest);
-      o.pad |= kOpNoStore;
-    }
-}
-
-// The queue as it will be launched.  Short lists (or kernels without two-deep forwarding): the first one that reads a virtual
-// buffer gets the storing definitions of ALL virtual buffers in front of it.  Long lists (may_virtualise): a tip x tip operation
-// whose result is written once in this list, read only later in it and not by the evaluation leaves its place; every reader of a
-// virtual buffer -- one left virtual by this list or by an earlier one -- computes it inside its own step (one per operation:
-// DevOp::pad bits 1-2, pending_inl) or gets the definition re-issued in front of it, not storing (the kernels forward the
-// results of the previous two operations in registers); what the evaluation edge reads is stored.
-void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
-{
-  I->pending_inl.clear();
-  const bool stored_deferred = settle_deferred(I, ee);
-  const int  n0 = (int)I->pending.size();
-  // (only launches of the LIST form: one- and two-operation launches -- records in the kernel arguments, the resident evaluators --
-  // run kernels without in-step children and without the second forwarding level's guarantees: a list must keep three
-  // operations even if each of its tip x tip operations leaves its place)
-  bool virtualise = may_virtualise && I->virt_min_ops > 0 && n0 >= I->virt_min_ops && n0 >= 3;
-  if (virtualise)
-  {
-    int stay = 0;
-    for (const DevOp &o : I->pending) stay += !(o.c1 < I->tips && o.c2 < I->tips);
-    virtualise = stay >= 3;
-  }
-  if (!virtualise && n_unstored(I) == 0) return;
-  if (!virtualise)
-  { // A short launch.  If it reads a virtual buffer, EVERY virtual buffer is stored now, in this one launch: the short launches
-    // of a tree search (SPR candidates, Lk(b), Br_Len_Opt) come in long runs after a full traversal, and one list of tip x tip
-    // operations in front of the first of them costs less than a launch of three operations -- instead of a resident command
-    // -- at each buffer's first use.
-    bool reads = false;
-    for (const DevOp &o : I->pending) reads = reads || (o.c1 >= I->tips && I->virt[o.c1]) || (o.c2 >= I->tips && I->virt[o.c2]);
-    if (ee) reads = reads || (ee->parent >= I->tips && I->virt[ee->parent]) || (ee->child >= I->tips && I->virt[ee->child]);
-    if (reads || stored_deferred) devirtualise_all(I); // (deferred buffers go with them; and with one that settle_deferred had to store)
-    // (a queued operation that WRITES a virtual buffer stores it: real again -- its old definition must never be stored over it)
-    for (const DevOp &o : I->pending)
-      if (I->virt[o.dest]) { I->virt[o.dest] = 0; --I->n_virtual; }
-    return;
-  }
-  std::vector<unsigned char> skip;
-  {
-    std::vector<int> n_dest(I->nbuf, 0), first_read(I->nbuf, -1);
-    for (int k = 0; k < n0; ++k)
-    {
-      const DevOp &o = I->pending[k];
-      ++n_dest[o.dest];
-      for (int c : {o.c1, o.c2})
-        if (c >= I->tips && first_read[c] < 0) first_read[c] = k;
-    }
-    skip.assign(n0, 0);
-    for (int k = 0; k < n0; ++k)
-    {
-      const DevOp &o = I->pending[k];
-      if (o.c1 < I->tips && o.c2 < I->tips && n_dest[o.dest] == 1 && first_read[o.dest] > k &&
-          !(ee && (ee->parent == o.dest || ee->child == o.dest)) &&
-          !I->keep_real_flag[o.dest])
-        skip[k] = 1;
-    }
-  }
-  std::vector<DevOp>     L;
-  std::vector<InlineDef> LI; // (parallel to L)
-  L.reserve((size_t)n0 + (size_t)I->n_virtual + 8);
-  LI.reserve(L.capacity());
-  const InlineDef none{-1, -1, -1, -1};
-  // both pipelined kernels compute ONE virtual child inside its reader's step (phyhip_nt2.hpp / phyhip_aa.hpp, INL); a second
-  // one is re-issued as a non-storing operation in front of the reader
-  const bool in_step = I->virt_inline && ((I->soa && I->nt_groups <= 2) || I->perm); // (the instantiations that exist: flush_impl)
-  bool       any_inl = false;
-  auto before_read = [&](int c, DevOp &reader, InlineDef &rin, int bit) {
-    if (c < I->tips || !I->virt[c]) return;
-    DevOp d = I->vdef[c];
-    I->mat_in_queue[d.pm1] = 1; I->mat_in_queue[d.pm2] = 1;
-    if (in_step && rin.a < 0 && reader.c1 != reader.c2)
-    {
-      rin = InlineDef{d.c1, d.c2, d.pm1, d.pm2};
-      reader.pad |= bit;
-      any_inl = true;
-      ++I->n_virt_recomputed;
-      return;
-    }
-    d.pad = kOpNoStore; ++I->n_virt_recomputed;
-    L.push_back(d); LI.push_back(none);
-  };
-  for (int k = 0; k < n0; ++k)
-  {
-    DevOp o = I->pending[k];
-    if (skip[k])
-    { // from here on the buffer is what this operation says; nothing is launched for it until somebody reads it
-      if (!I->virt[o.dest]) { I->virt[o.dest] = 1; ++I->n_virtual; }
-      o.pad = 0;
-      I->vdef[o.dest] = o;
-      stamp_definition(I, o.dest);
-      ++I->n_virt_skipped;
-      continue;
-    }
-    InlineDef in = none;
-    before_read(o.c1, o, in, kOpInl1);
-    if (o.c2 != o.c1) before_read(o.c2, o, in, kOpInl2);
-    L.push_back(o); LI.push_back(in);
-    if (I->virt[o.dest]) { I->virt[o.dest] = 0; --I->n_virtual; } // (a storing operation: the buffer is real again)
-  }
-  auto store_now = [&](int b) { // what is read from memory behind this launch (or by its evaluation): stored
-    if (b < I->tips || !I->virt[b]) return;
-    DevOp d = I->vdef[b];
-    d.pad = 0;
-    I->virt[b] = 0; --I->n_virtual; ++I->n_virt_material;
-    I->mat_in_queue[d.pm1] = 1; I->mat_in_queue[d.pm2] = 1;
-    L.push_back(d); LI.push_back(none);
-  };
-  for (int b : I->keep_real) store_now(b);
-  if (ee)
-    for (int side : {ee->parent, ee->child}) store_now(side);
-  // The pipelined kernels pad an odd list by running its last operation once more (flush_impl), at a position where the result
-  // of the operation THREE steps back is no longer in registers: a child of the last operation produced there is then read from
-  // memory -- so it must have been stored (two non-storing re-issues in front of a reader; reachable without in-step children)
-  if ((L.size() & 1) && L.size() >= 3)
-  {
-    DevOp       &d1 = L[L.size() - 3];
-    const DevOp &rd = L.back();
-    if ((d1.pad & kOpNoStore) && (rd.c1 == d1.dest || rd.c2 == d1.dest))
-    {
-      d1.pad &= ~kOpNoStore;
-      if (I->virt[d1.dest]) { I->virt[d1.dest] = 0; --I->n_virtual; ++I->n_virt_material; }
-    }
-  }
-  if (I->defer_stores) defer_forwarded(I, ee, L, list_chains(I, L, LI));
-  I->pending.swap(L);
-  if (any_inl) I->pending_inl.swap(LI);
-  // (the rewritten list is launched as it stands: flush_impl.  A SHORT list leaves here as it came, its stored definitions still
-  // in front and n_front still counting them -- phyhip_update_eigen_lr rewrites its queue once without launching and the flush
-  // rewrites it again: the second settle_deferred must still know them, and a definition stored then must still find its place)
-  I->n_front = 0;
-}
-
 // Host-computed matrices queued by phyhip_set_transition_matrix: one launch per kUploadBatch of them.
 int flush_uploads(Instance *I)
 {
@@ -549,7 +199,7 @@ static void retire_queue(Instance *I, bool fold_pm)
     I->pm_shadow.clear();
   }
   I->pending.clear();
-  I->n_front = 0;
+  I->unstored.n_front = 0;
   std::fill(I->mat_in_queue.begin(), I->mat_in_queue.end(), 0);
 }
 
@@ -1333,7 +983,7 @@ static int flush_impl(Instance *I, const EdgeEval *ee)
   // kernels with two-deep register forwarding leaves its own tip x tip results virtual (rewrite_pending)
   rewrite_pending(I, ee, (I->soa || I->perm) && !I->generic_nt && I->prefetch_dist == 2 && !I->class_axis && !I->generic_loop &&
                              !I->ablate && !I->no_loads);
-  keep_real_clear(I);
+  I->unstored.keep_clear();
   const int n_ops = f.n_ops = (int)I->pending.size();
   int       rc = 0;
   if (n_ops > 0 || ee || !I->pm_idx.empty() || !I->up_idx.empty()) I->stream_dirty = true;

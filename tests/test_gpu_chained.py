@@ -27,7 +27,7 @@ LIST_LENGTH = {(9, 2): 5, (12, 1): 8}
 
 
 class Replay:
-    """The rewritten list of a one-sided Lk(NULL) as phyhip_queue.hip builds it, on node numbers.  m: its length; virt: nodes left
+    """The rewritten list of a one-sided Lk(NULL) as phyhip_unstored.hip builds it, on node numbers.  m: its length; virt: nodes left
     virtual; deferred / chained: {node: [child nodes]}; key: node -> (edge, side); order: the nodes in post-order."""
 
     def __init__(self, ot, min_ops=3):

@@ -24,7 +24,7 @@ LIST_LENGTH = {(9, 2): 5, (12, 1): 8}
 
 
 def replay(ot, min_ops=3):
-    """The rewritten list of a one-sided Lk(NULL) as phyhip_queue.hip builds it (rewrite_pending, then defer_forwarded), on node
+    """The rewritten list of a one-sided Lk(NULL) as phyhip_unstored.hip builds it (rewrite_pending, then defer_forwarded), on node
     numbers: (list length, {deferred node: (edge, side, [child nodes])}, number of virtual buffers)."""
     n, r = ot.n, ot.tip_root
     v0 = ot.adj[r][0][0]

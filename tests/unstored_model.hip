@@ -1,19 +1,26 @@
-// tests/virt_chain_model.hip -- test infrastructure (CPU only, no device is touched): the symbolic model of tests/virt_defer_model.hip
-// with the CHAINED class of unstored buffer switched on (Instance::chain_min_ops, chained, def_seq; phyml_amd/csrc/phyhip_queue.hip:
-// defer_forwarded's second pass, settle_chained, store_definition).  It links the BUILT library, builds an Instance by hand, feeds it random queues,
-// readers and writers, and after every "launch" interprets the rewritten queue with the kernels' forwarding rules (last two results
-// in registers, in-step children, non-storing operations) on symbolic values, in lockstep with the plain semantics.  After every
-// launch:
-//   * the definition of every unstored buffer, evaluated over its inputs' definitions recursively (stored inputs: device memory),
-//     is the buffer's plain value;
-//   * every input of a deferred or chained definition is a tip, stored, or unstored under an older sequence number (a deferred
-//     definition is made over stored inputs; a list that chains may leave one of them chained behind it);
-//   * every written buffer is stored or unstored; a reader finds the plain value in memory; the counters match the flags.
-// Events: replayed post-orders in which every edge has its own matrix (the lists that chain), random long and short lists, short
-// lists that write a buffer in the middle of a chain (the buffer itself or one of its inputs), a reader of a chain's last buffer
-// before any reader of its first -- across launches and inside one queue, in both orders --, readers that rewrite the queue once
-// without launching it before the launch rewrites it again (phyhip_update_eigen_lr), tip and matrix changes, threshold moves.
-// Built and run by tests/test_virt_chain_model.py:  virt_chain_model <seed> <events> <tips> <soa 0|1> [in-step children 1|0]
+// tests/unstored_model.hip -- test infrastructure (CPU only, no device is touched): the symbolic model of the unstored-buffer
+// bookkeeping of libphyhip.so (phyml_amd/csrc/phyhip_unstored.hip: rewrite_pending, devirtualise*, settle_deferred, defer_forwarded;
+// the table: Unstored, phyhip_host.hpp).  It links the BUILT library, builds an Instance by hand -- the table sized as
+// phyhip_create_instance sizes it --, feeds it random queues, readers and writers, and after every "launch" interprets the rewritten
+// queue with the kernels' forwarding rules (last two results in registers, in-step children, non-storing operations) on symbolic
+// values, in lockstep with the plain semantics (every operation stored, in queue order):
+//   * a stale buffer must never be read from memory; the evaluation edge sees the plain semantics' values;
+//   * what a launch leaves in memory -- or unstored, through its definition -- must be what the plain semantics hold for that buffer.
+// The first argument is the highest class of unstored buffer switched on; the checks and events that depend on it:
+//   1  virtual.  Every written buffer is stored or virtual.
+//   2  + deferred (Unstored::defer_stores).  A deferred definition's inputs are in memory and are the plain values they had when the
+//      definition was made; its value over them is the buffer's plain value; the counters match the classes.  Events: replayed
+//      post-orders (they rewrite inputs and buffers in the order a repeated Lk(NULL) does), short lists that write an input of a
+//      deferred buffer.
+//   3  + chained (Unstored::chain_min_ops).  Instead of class 2's input checks: the definition of every unstored buffer, evaluated
+//      over its inputs' definitions recursively, is the buffer's plain value; every input of a deferred or chained definition is a
+//      tip, stored, or unstored under an older sequence number.  Events: the replayed post-orders give every edge its own matrix
+//      (the lists that chain); short lists that write a buffer in the middle of a chain; a reader of a chain's last buffer before
+//      any reader of its first -- across launches and inside one queue, in both orders --; readers that rewrite the queue once
+//      without launching it before the launch rewrites it again (phyhip_update_eigen_lr).
+// Matrices and tip rows change through the store-first route (devirtualise_matrix / devirtualise_tip + a launch); the snapshot
+// route of the matrix setters needs a device and is covered by tests/test_gpu_virtual.py.
+// Built and run through tests/unstored_model.py:  unstored_model <class 1|2|3> <seed> <events> <tips> <soa 0|1> [in-step children 1|0]
 #include "../phyml_amd/csrc/phyhip_host.hpp"
 
 #include <algorithm>
@@ -21,6 +28,7 @@
 #include <random>
 
 using namespace phyhip_host;
+using U = Unstored;
 
 static uint64_t H(uint64_t a, uint64_t b, uint64_t c, uint64_t d)
 {
@@ -37,29 +45,37 @@ static uint64_t H(uint64_t a, uint64_t b, uint64_t c, uint64_t d)
 struct Model
 {
   Instance *I;
+  int       cls;                        // the highest class switched on
   std::vector<uint64_t> tipv, matv;     // versions of the tip rows / matrices
   std::vector<uint64_t> ref, dev;       // plain semantics / device memory per buffer
   std::vector<char>     written;        // the buffer has been the destination of a queued operation
   std::vector<DevOp>    queued;         // what the caller queued since the last launch (plain semantics are applied at launch)
+  std::vector<char>     was_def;        // below class 3: the buffer was deferred after the previous launch
+  std::vector<DevOp>    seen_def;       // ... with this definition
+  std::vector<uint64_t> in1, in2;       // ... whose inputs had these plain values when it was made
   long                  n_launch = 0, n_instep = 0, n_nostore = 0, n_pad = 0;
   mutable long          max_chain = 0;
 
+  const Unstored &u() const { return I->unstored; }
+  bool is(int b, U::Class c) const { return u().class_of(b) == c; }
   uint64_t tipval(int t) const { return H(1, (uint64_t)t, tipv[t], 0); }
   uint64_t def_value(const DevOp &d) const { return H(tipval(d.c1), tipval(d.c2), matv[d.pm1], matv[d.pm2]); }
+  uint64_t memval(int c) const { return c < I->tips ? tipval(c) : dev[c]; }
+  uint64_t refval(int c) const { return c < I->tips ? tipval(c) : ref[c]; }
 
   // what a buffer IS after a launch: device memory, or its definition over what its inputs are
   uint64_t value(int c, int depth = 0) const
   {
     if (c < I->tips) return tipval(c);
-    if (!is_unstored(I, c)) return dev[c];
+    if (!u().is_unstored(c)) return dev[c];
     if (depth > I->nbuf) die("definitions form a cycle", c);
-    const DevOp &d = unstored_def(I, c);
+    const DevOp &d = u().def(c);
     return H(value(d.c1, depth + 1), value(d.c2, depth + 1), matv[d.pm1], matv[d.pm2]);
   }
 
   [[noreturn]] void die(const char *what, int a = -1, int b = -1) const
   {
-    fprintf(stderr, "VIRT_CHAIN_MODEL FAIL: %s (%d, %d) after %ld launches\n", what, a, b, n_launch);
+    fprintf(stderr, "UNSTORED_MODEL FAIL (class %d): %s (%d, %d) after %ld launches\n", cls, what, a, b, n_launch);
     exit(1);
   }
 
@@ -79,7 +95,7 @@ struct Model
       }
     };
     rewrite_pending(I, ee, true);
-    keep_real_clear(I); // (as flush_impl does)
+    I->unstored.keep_clear(); // (as flush_impl does)
     const std::vector<DevOp> &L = I->pending;
     const bool has_inl = !I->pending_inl.empty();
     if (has_inl && I->pending_inl.size() != L.size()) die("pending_inl is not parallel to pending");
@@ -167,98 +183,110 @@ struct Model
     ref = cur;
     queued.clear();
     I->pending.clear();
-    I->n_front = 0; // (as retire_queue does)
+    I->unstored.n_front = 0; // (as retire_queue does)
     std::fill(I->mat_in_queue.begin(), I->mat_in_queue.end(), 0);
     ++n_launch;
-    // memory and definitions after the launch
-    int nv = 0;
+    check_after_launch(dest_now);
+  }
+
+  // memory and definitions after a launch
+  void check_after_launch(const std::vector<char> &dest_now)
+  {
+    int n[4] = {0, 0, 0, 0};
     for (int b = I->tips; b < I->nbuf; ++b)
     {
-      if (I->virt[b])
+      ++n[u().class_of(b)];
+      if (u().class_of(b) > cls) die("a buffer is in a class that is switched off", b, u().class_of(b));
+      if (is(b, U::kVirtual))
       {
-        ++nv;
-        const DevOp &d = I->vdef[b];
+        const DevOp &d = u().def(b);
         if (d.c1 >= I->tips || d.c2 >= I->tips) die("a virtual buffer's definition is not tip x tip", b);
         if (def_value(d) != ref[b]) die("a virtual buffer's definition is not its plain value", b);
       }
-      else if (!is_unstored(I, b) && written[b] && dev[b] != ref[b]) die("a buffer is neither stored nor unstored", b);
+      else if ((cls < 2 || !u().is_unstored(b)) && written[b] && dev[b] != ref[b])
+        die(cls < 2 ? "a buffer is neither stored nor virtual" : "a buffer is neither stored nor unstored", b);
     }
-    if (nv != I->n_virtual) die("n_virtual does not count the flags", nv, I->n_virtual);
-    int nd = 0, nc = 0;
+    for (U::Class c : {U::kVirtual, U::kDeferred, U::kChained})
+      if (n[c] != u().n(c)) die("the count of a class does not count its buffers", (int)c, u().n(c));
+    if (n[U::kVirtual] + n[U::kDeferred] + n[U::kChained] != u().n_unstored()) die("n_unstored does not count the unstored buffers");
     for (int b = I->tips; b < I->nbuf; ++b)
     {
-      if (I->deferred[b] + I->chained[b] + I->virt[b] > 1) die("a buffer is in two classes", b);
-      if (I->deferred[b])
-      {
-        ++nd;
-        const DevOp &d = I->ddef[b];
-        if (d.pad != 0) die("a deferred definition carries flags", b);
+      if (!is(b, U::kDeferred)) was_def[b] = 0;
+      if (!u().is_unstored(b) || is(b, U::kVirtual)) continue;
+      const DevOp &d = u().def(b);
+      if (d.pad != 0) die(is(b, U::kDeferred) ? "a deferred definition carries flags" : "a chained definition carries flags", b);
+      if (is(b, U::kDeferred))
         for (int c : {d.c1, d.c2})
-          if (c >= I->tips && I->virt[c]) die("a deferred definition reads a virtual buffer", b, c);
+          if (c >= I->tips && is(c, U::kVirtual)) die("a deferred definition reads a virtual buffer", b, c);
+      if (cls < 3)
+      { // (a deferred definition is one step over stored inputs, and stays so)
+        for (int c : {d.c1, d.c2})
+          if (c >= I->tips && u().is_unstored(c)) die("a deferred definition reads an unstored buffer", b, c);
+        const bool fresh = !was_def[b] || dest_now[b] || memcmp(&seen_def[b], &d, sizeof d) != 0;
+        if (fresh) { in1[b] = refval(d.c1); in2[b] = refval(d.c2); seen_def[b] = d; was_def[b] = 1; }
+        if (memval(d.c1) != in1[b] || memval(d.c2) != in2[b]) die("a deferred definition's input is not in memory as it was when the definition was made", b);
+        if (refval(d.c1) != in1[b] || refval(d.c2) != in2[b]) die("a deferred definition's input has another plain value than when the definition was made", b);
+        if (H(in1[b], in2[b], matv[d.pm1], matv[d.pm2]) != ref[b]) die("a deferred definition is not its buffer's plain value", b);
+        continue;
       }
-      if (I->deferred[b] || I->chained[b])
-        for (int c : {I->ddef[b].c1, I->ddef[b].c2})
-        { // (a deferred definition is made over stored inputs; a list that chains may leave one of them chained behind it)
-          if (c < I->tips) continue;
-          if (is_unstored(I, c) ? I->def_seq[c] >= I->def_seq[b] : (!written[c] || dev[c] != ref[c]))
-            die("a definition's input is neither stored nor unstored under an older sequence number", b, c);
-        }
-      if (I->chained[b])
+      for (int c : {d.c1, d.c2})
+      { // (a deferred definition is made over stored inputs; a list that chains may leave one of them chained behind it)
+        if (c < I->tips) continue;
+        if (u().is_unstored(c) ? u().seq(c) >= u().seq(b) : (!written[c] || dev[c] != ref[c]))
+          die("a definition's input is neither stored nor unstored under an older sequence number", b, c);
+      }
+      if (is(b, U::kChained))
       {
-        ++nc;
-        const DevOp &d = I->ddef[b];
-        if (d.pad != 0) die("a chained definition carries flags", b);
         int len = 1; // (the longest chain of definitions that read buffers, ending in a chained one: a figure)
         for (int c = b;;)
         {
-          const DevOp &e = I->ddef[c];
-          auto link = [&](int x) { return x >= I->tips && (I->chained[x] || I->deferred[x]); };
+          const DevOp &e = u().def(c);
+          auto link = [&](int x) { return x >= I->tips && (is(x, U::kChained) || is(x, U::kDeferred)); };
           const int nx = link(e.c1) ? e.c1 : link(e.c2) ? e.c2 : -1;
           if (nx < 0) break;
           c = nx; ++len;
         }
         max_chain = std::max(max_chain, (long)len);
       }
-      if (is_unstored(I, b) && value(b) != ref[b]) die("an unstored buffer's definition, evaluated over its inputs' definitions, is not its plain value", b);
+      if (value(b) != ref[b]) die("an unstored buffer's definition, evaluated over its inputs' definitions, is not its plain value", b);
     }
-    if (nd != I->n_deferred) die("n_deferred does not count the flags", nd, I->n_deferred);
-    if (nc != I->n_chained) die("n_chained does not count the flags", nc, I->n_chained);
-    if (I->n_def_skipped != (unsigned long long)I->n_deferred + I->n_def_material + I->n_def_dropped)
+    const U::Counters &cd = u().counters(U::kDeferred), &cc = u().counters(U::kChained);
+    if (cd.skipped != (unsigned long long)u().n(U::kDeferred) + cd.material + cd.dropped)
       die("deferred counters: deferred so far != deferred now + stored on demand + dropped");
-    if (I->n_chain_skipped != (unsigned long long)I->n_chained + I->n_chain_material + I->n_chain_dropped)
+    if (cc.skipped != (unsigned long long)u().n(U::kChained) + cc.material + cc.dropped)
       die("chained counters: chained so far != chained now + stored on demand + dropped");
   }
 };
 
 int main(int argc, char **argv)
 {
-  const unsigned seed = argc > 1 ? (unsigned)atoi(argv[1]) : 1u;
-  const int      events = argc > 2 ? atoi(argv[2]) : 2000, tips = argc > 3 ? atoi(argv[3]) : 12;
-  const bool     soa = argc > 4 ? atoi(argv[4]) != 0 : true;
-  const bool     in_step = argc > 5 ? atoi(argv[5]) != 0 : true; // 0: every virtual child re-issued as a step of its own (diag: PHYHIP_VIRT_INLINE=0)
+  const int      cls = argc > 1 ? atoi(argv[1]) : 3;
+  const unsigned seed = argc > 2 ? (unsigned)atoi(argv[2]) : 1u;
+  const int      events = argc > 3 ? atoi(argv[3]) : 2000, tips = argc > 4 ? atoi(argv[4]) : 12;
+  const bool     soa = argc > 5 ? atoi(argv[5]) != 0 : true;
+  const bool     in_step = argc > 6 ? atoi(argv[6]) != 0 : true; // 0: every virtual child re-issued as a step of its own (diag: PHYHIP_VIRT_INLINE=0)
+  if (cls < 1 || cls > 3 || tips < 2) { fprintf(stderr, "usage: unstored_model <class 1|2|3> <seed> <events> <tips> <soa 0|1> [in-step 1|0]\n"); return 2; }
   std::mt19937   rng(seed);
   auto rnd = [&](int n) { return (int)(rng() % (unsigned)n); };
 
   Instance *I = new Instance();
-  I->tips = tips; I->nbuf = 3 * tips; I->nmat = 4 * tips + 2; I->nmat_all = I->nmat + 2 * (I->nbuf - I->tips);
+  Unstored &u = I->unstored;
+  I->tips = tips; I->nbuf = 3 * tips;
+  I->nmat = cls >= 3 ? 4 * tips + 2 : 2 * tips; // (class 3: enough matrices for a post-order with one per edge)
+  I->nmat_all = I->nmat + 2 * (I->nbuf - I->tips);
   I->S = soa ? 4 : 20; I->C = 4; I->soa = soa; I->perm = !soa; I->nt_groups = 2; I->prefetch_dist = 2;
-  I->virt.assign(I->nbuf, 0);
-  I->keep_real_flag.assign(I->nbuf, 0);
-  I->vdef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
+  u.resize(I->nbuf);
   I->mat_in_queue.assign(I->nmat_all, 0);
-  I->virt_min_ops = 3 + rnd(6);
-  I->deferred.assign(I->nbuf, 0);
-  I->ddef.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0});
-  I->defer_stores = true;
-  I->chained.assign(I->nbuf, 0);
-  I->def_seq.assign(I->nbuf, 0);
-  I->chain_min_ops = 3 + rnd(6);
+  u.virt_min_ops = 3 + rnd(6);
+  u.defer_stores = cls >= 2;
+  u.chain_min_ops = cls >= 3 ? 3 + rnd(6) : 0;
   I->virt_inline = in_step;
 
   Model M;
-  M.I = I;
+  M.I = I; M.cls = cls;
   M.tipv.assign(tips, 1); M.matv.assign(I->nmat_all, 1);
   M.ref.assign(I->nbuf, 0); M.dev.assign(I->nbuf, 0); M.written.assign(I->nbuf, 0);
+  M.was_def.assign(I->nbuf, 0); M.seen_def.assign(I->nbuf, DevOp{0, 0, 0, 0, 0, 0}); M.in1.assign(I->nbuf, 0); M.in2.assign(I->nbuf, 0);
 
   auto queue_op = [&](int dest, int c1, int c2, int pm1 = -1, int pm2 = -1) {
     DevOp o{dest, c1, c2, pm1 < 0 ? rnd(I->nmat) : pm1, pm2 < 0 ? rnd(I->nmat) : pm2, 0};
@@ -294,7 +322,8 @@ int main(int argc, char **argv)
     }
   };
   // A post-order over distinct buffers, as Post_Order_Lk emits one: every result is read once, mostly by one of the next two
-  // operations; each edge has its own matrix.  Replayed, it rewrites inputs and buffers in the same order -- a repeated Lk(NULL).
+  // operations.  Replayed, it rewrites inputs and buffers in the same order -- a repeated Lk(NULL).  Class 3: every edge has its
+  // own matrix (a one-sided traversal, the lists that chain); below, matrices are drawn at random.
   std::vector<std::vector<DevOp>> orders;
   auto make_order = [&]() {
     std::vector<int> bufs;
@@ -303,9 +332,12 @@ int main(int argc, char **argv)
     const int n = std::min((int)bufs.size(), 3 + rnd(2 * tips - 3 > 0 ? 2 * tips - 3 : 1));
     std::vector<DevOp> ops;
     std::vector<int>   open; // results nobody has read yet
-    std::vector<int>   mats; // (every edge has its own matrix: a one-sided traversal, the lists that chain)
-    for (int m = 0; m < I->nmat; ++m) mats.push_back(m);
-    std::shuffle(mats.begin(), mats.end(), rng);
+    std::vector<int>   mats;
+    if (cls >= 3)
+    {
+      for (int m = 0; m < I->nmat; ++m) mats.push_back(m);
+      std::shuffle(mats.begin(), mats.end(), rng);
+    }
     for (int k = 0; k < n; ++k)
     {
       auto take = [&](bool newest) {
@@ -316,39 +348,44 @@ int main(int argc, char **argv)
         return c;
       };
       const int c1 = take(true), c2 = take(false);
-      ops.push_back(DevOp{bufs[k], c1, c2, mats[2 * k], mats[2 * k + 1], 0});
+      const int m1 = cls >= 3 ? mats[2 * k] : rnd(I->nmat), m2 = cls >= 3 ? mats[2 * k + 1] : rnd(I->nmat);
+      ops.push_back(DevOp{bufs[k], c1, c2, m1, m2, 0});
       open.push_back(bufs[k]);
     }
     return ops;
   };
-  for (int k = 0; k < 3; ++k) orders.push_back(make_order());
-  // a buffer whose definition reads buffers (deferred or chained); the ends of the chained definitions by sequence number
+  if (cls >= 2)
+    for (int k = 0; k < 3; ++k) orders.push_back(make_order());
+  auto is = [&](int b, U::Class c) { return u.class_of(b) == c; };
+  // a deferred or chained buffer -- class 3: one whose definition reads buffers; the ends of the chained definitions by sequence number
   auto any_dependant = [&]() {
     std::vector<int> d;
     for (int b = tips; b < I->nbuf; ++b)
-      if ((I->deferred[b] || I->chained[b]) && (I->ddef[b].c1 >= tips || I->ddef[b].c2 >= tips)) d.push_back(b);
+      if ((is(b, U::kDeferred) || is(b, U::kChained)) && (cls < 3 || u.def(b).c1 >= tips || u.def(b).c2 >= tips)) d.push_back(b);
     return d.empty() ? -1 : d[rnd((int)d.size())];
   };
   auto chain_end = [&](bool last) {
     int e = -1;
     for (int b = tips; b < I->nbuf; ++b)
-      if (I->chained[b] && (e < 0 || (last ? I->def_seq[b] > I->def_seq[e] : I->def_seq[b] < I->def_seq[e]))) e = b;
+      if (is(b, U::kChained) && (e < 0 || (last ? u.seq(b) > u.seq(e) : u.seq(b) < u.seq(e)))) e = b;
     return e;
   };
   // phyhip_update_eigen_lr stores what its products read, rewrites the queue ONCE WITHOUT LAUNCHING (a short list: it decides on
-  // the queue as it will be launched) and flushes afterwards, which rewrites it again: the reader events do the same half of the time
+  // the queue as it will be launched) and flushes afterwards, which rewrites it again: from class 3 the reader events do the same
+  // half of the time
   long n_double = 0;
   auto reader = [&](int b) {
     devirtualise(I, b);
-    if (rnd(2)) { rewrite_pending(I, nullptr, false); ++n_double; }
+    if (cls >= 3 && rnd(2)) { rewrite_pending(I, nullptr, false); ++n_double; }
   };
   auto read_back = [&](int b, const char *what) {
-    if (is_unstored(I, b) || M.dev[b] != M.ref[b]) M.die(what, b);
+    if (u.is_unstored(b) || M.dev[b] != M.ref[b]) M.die(what, b);
   };
   long n_input_writes = 0, n_replays = 0, n_mid_writes = 0, n_end_reads = 0;
+  const int kinds = cls >= 3 ? 17 : cls == 2 ? 14 : 10; // (events 10-13: from class 2; 14-16: from class 3)
   for (int ev = 0; ev < events; ++ev)
   {
-    switch (rnd(17))
+    switch (rnd(kinds))
     {
       case 10: case 11: case 14:
       { // a post-order traversal with its evaluation at the root, now and then a new one
@@ -369,12 +406,13 @@ int main(int argc, char **argv)
         // middle of a chain, when the input is chained itself; then a reader of the dependant
         const int b = any_dependant();
         if (b < 0) break;
-        const DevOp d = I->ddef[b];
+        const DevOp d = u.def(b);
         const int   c = d.c1 >= tips ? d.c1 : d.c2;
+        if (c < tips) break;
         M.launch(nullptr);
-        if (!I->deferred[b] && !I->chained[b]) break;
+        if (!is(b, U::kDeferred) && !is(b, U::kChained)) break;
         const uint64_t old = M.ref[b];
-        n_mid_writes += is_unstored(I, c);
+        n_mid_writes += cls >= 3 && u.is_unstored(c);
         if (rnd(2)) queue_op(c, rnd(tips), rnd(tips));
         else
         {
@@ -388,7 +426,9 @@ int main(int argc, char **argv)
         {
           reader(b);
           M.launch(nullptr);
-          if (is_unstored(I, b) || M.dev[b] != old) M.die("an unstored buffer whose input was rewritten does not read back its old value", b, c);
+          if (u.is_unstored(b) || M.dev[b] != old)
+            M.die(cls < 3 ? "a deferred buffer whose input was rewritten does not read back its old value"
+                          : "an unstored buffer whose input was rewritten does not read back its old value", b, c);
         }
         break;
       }
@@ -437,8 +477,7 @@ int main(int argc, char **argv)
         devirtualise_matrix(I, m);
         M.launch(nullptr);
         for (int b = tips; b < I->nbuf; ++b)
-          if (is_unstored(I, b) && (unstored_def(I, b).pm1 == m || unstored_def(I, b).pm2 == m))
-            M.die("an unstored buffer still reads a matrix that changes", b, m);
+          if (u.is_unstored(b) && (u.def(b).pm1 == m || u.def(b).pm2 == m)) M.die("an unstored buffer still reads a matrix that changes", b, m);
         ++M.matv[m];
         break;
       }
@@ -449,29 +488,29 @@ int main(int argc, char **argv)
         devirtualise_tip(I, t);
         M.launch(nullptr);
         for (int b = tips; b < I->nbuf; ++b)
-          if (is_unstored(I, b) && (unstored_def(I, b).c1 == t || unstored_def(I, b).c2 == t))
-            M.die("an unstored buffer still reads a tip row that changes", b, t);
+          if (u.is_unstored(b) && (u.def(b).c1 == t || u.def(b).c2 == t)) M.die("an unstored buffer still reads a tip row that changes", b, t);
         ++M.tipv[t];
         break;
       }
       case 8:
         if (rnd(4) == 0)
         { // everything stored (phyhip_set_virtual_buffers(0) / another threshold)
-          I->virt_min_ops = 0;
+          u.virt_min_ops = 0;
           devirtualise_all(I);
           M.launch(nullptr);
-          if (n_unstored(I) != 0) M.die("devirtualise_all left unstored buffers");
-          I->virt_min_ops = 1 + rnd(12);
-          I->chain_min_ops = rnd(5) ? 3 + rnd(10) : 0; // (the chained class has its own threshold; 0: off, what is chained stays until settled)
+          if (u.n_unstored() != 0) M.die("devirtualise_all left unstored buffers");
+          u.virt_min_ops = 1 + rnd(12);
+          if (cls >= 3) u.chain_min_ops = rnd(5) ? 3 + rnd(10) : 0; // (the chained class has its own threshold; 0: off, what is chained stays until settled)
         }
         break;
       default: queue_traversal(6 + rnd(20)); break;
     }
   }
   M.launch(nullptr);
-  printf("VIRT_CHAIN_MODEL OK seed %u: %ld launches, %llu stores skipped, %ld in-step children, %ld non-storing operations, %llu stored on demand, %ld odd lists re-ran their last operation, %llu stores deferred, %llu deferred stored on demand, %llu deferred dropped, %ld input writes, %ld replays, %llu stores chained, %llu chained stored on demand, %llu chained dropped, %ld longest chain, %ld writes under a chained input, %ld reads of chain ends, %ld queues rewritten twice\n",
-         seed, M.n_launch, (unsigned long long)I->n_virt_skipped, M.n_instep, M.n_nostore, (unsigned long long)I->n_virt_material, M.n_pad,
-         (unsigned long long)I->n_def_skipped, (unsigned long long)I->n_def_material, (unsigned long long)I->n_def_dropped, n_input_writes, n_replays,
-         (unsigned long long)I->n_chain_skipped, (unsigned long long)I->n_chain_material, (unsigned long long)I->n_chain_dropped, M.max_chain, n_mid_writes, n_end_reads, n_double);
+  const U::Counters &cv = u.counters(U::kVirtual), &cd = u.counters(U::kDeferred), &cc = u.counters(U::kChained);
+  printf("UNSTORED_MODEL OK class %d seed %u: %ld launches, %llu stores skipped, %ld in-step children, %ld non-storing operations, %llu stored on demand, %ld odd lists re-ran their last operation, %llu stores deferred, %llu deferred stored on demand, %llu deferred dropped, %ld input writes, %ld replays, %llu stores chained, %llu chained stored on demand, %llu chained dropped, %ld longest chain, %ld writes under a chained input, %ld reads of chain ends, %ld queues rewritten twice\n",
+         cls, seed, M.n_launch, cv.skipped, M.n_instep, M.n_nostore, cv.material, M.n_pad, cd.skipped, cd.material, cd.dropped, n_input_writes,
+         n_replays, cc.skipped, cc.material, cc.dropped, M.max_chain, n_mid_writes, n_end_reads, n_double);
+  delete I;
   return 0;
 }
