@@ -374,10 +374,10 @@ static int build_instance(Instance *I, const hipDeviceProp_t &prop)
                                                        (size_t)I->C * I->S * I->S * sizeof(double) * 4));
   rc = I->ring.init(chunk);
   if (rc) return rc;
-  I->ring.before_rotate = [I]() { return I->up_idx.empty() ? 0 : flush_uploads(I); };
+  I->ring.before_rotate = [I]() { return I->uploads.empty() ? 0 : flush_uploads(I); };
   I->mat_in_queue.assign(I->nmat_all, 0);
-  I->up_slot.assign(I->nmat, -1);
-  I->pm_slot.assign(I->nmat, -1);
+  I->uploads.reset(I->nmat);
+  I->rebuilds.reset(I->nmat);
   I->slot_ops.assign(I->ops_slots, std::vector<DevOp>());
   I->slot_inl.assign(I->ops_slots, std::vector<InlineDef>());
   if (const char *e = diag_env("PHYHIP_VIRT_INLINE")) I->virt_inline = atoi(e) != 0;
@@ -794,8 +794,8 @@ static int matrices_touch(Instance *I, const int *idx, int count, std::vector<in
       if (i1 < 0 && i2 < 0) continue;
       if (shadow->empty()) shadow->assign(count, -1);
       // (one snapshot per matrix and call; a second dependant of a matrix, or a definition that reads it twice, is stored instead)
-      const bool free1 = i1 < 0 || ((*shadow)[i1] < 0 && I->pm_slot[d.pm1] < 0 && I->up_slot[d.pm1] < 0);
-      const bool free2 = i2 < 0 || ((*shadow)[i2] < 0 && I->pm_slot[d.pm2] < 0 && I->up_slot[d.pm2] < 0);
+      const bool free1 = i1 < 0 || ((*shadow)[i1] < 0 && no_refresh_queued(I, d.pm1));
+      const bool free2 = i2 < 0 || ((*shadow)[i2] < 0 && no_refresh_queued(I, d.pm2));
       if (!free1 || !free2 || (i1 >= 0 && i2 >= 0 && d.pm1 == d.pm2)) { devirtualise(I, b); continue; }
       if (i1 >= 0) { (*shadow)[i1] = shadow_slot(I, b, 0); d.pm1 = shadow_slot(I, b, 0); }
       if (i2 >= 0) { (*shadow)[i2] = shadow_slot(I, b, 1); d.pm2 = shadow_slot(I, b, 1); }
@@ -848,23 +848,15 @@ int phyhip_update_transition_matrices(int instance, int eigenIndex, const int *p
   // Deferred like the partial updates: SPR refreshes three matrices per regraft candidate (src/spr.c:643-646);
   // they are rebuilt by ONE pmat_kernel launch right before the traversal kernel that reads them.
   for (int i = 0; i < count; ++i)
-    if (I->up_slot[probabilityIndices[i]] >= 0)
-    { // an upload of the same matrix is still queued: it must land before the rebuild
+    if (I->uploads.queued(probabilityIndices[i]))
+    { // an upload of the same matrix is still queued: it must land before the rebuild (the two tables' invariant, phyhip_host.hpp)
       if ((rc = flush_uploads(I))) return rc;
       break;
     }
   for (int i = 0; i < count; ++i)
   {
-    const int m = probabilityIndices[i];
-    if (I->pm_slot[m] >= 0) I->pm_len[I->pm_slot[m]] = edgeLengths[i]; // last length wins
-    else
-    {
-      I->pm_slot[m] = (int)I->pm_idx.size();
-      I->pm_idx.push_back(m);
-      I->pm_len.push_back(edgeLengths[i]);
-      I->pm_shadow.push_back(-1);
-    }
-    if (!shadow.empty() && shadow[i] >= 0) { I->pm_shadow[I->pm_slot[m]] = shadow[i]; ++I->n_pm_shadow; }
+    I->rebuilds.put(probabilityIndices[i], edgeLengths[i]); // last length wins
+    if (!shadow.empty() && shadow[i] >= 0) I->rebuilds.want_snapshot(probabilityIndices[i], shadow[i]);
   }
   // A whole-tree batch (Update_All_PMat, src/lk.c:500-512) is launched now rather than with the traversal: the device
   // rebuilds the matrices while the host walks the tree and fills the operation list.
@@ -897,23 +889,16 @@ int phyhip_set_transition_matrix(int instance, int matrixIndex, const double *in
   std::vector<int> shadow;
   int rc = matrices_touch(I, &matrixIndex, 1, &shadow);
   if (rc) return rc;
-  if (I->pm_slot[matrixIndex] >= 0 && (rc = flush_pmats(I))) return rc; // keep rebuild-then-upload order
+  if (I->rebuilds.queued(matrixIndex) && (rc = flush_pmats(I))) return rc; // keep rebuild-then-upload order (the two tables' invariant)
   const size_t bytes = (size_t)I->C * I->S * I->S * sizeof(double);
   void        *st    = nullptr;
   rc = I->ring.alloc(bytes, I->stream, &st);
   if (rc) return rc;
   memcpy(st, inMatrix, bytes);
   // queued: the matrices set since the last launch travel together (SPR sets three per candidate, src/spr.c:643-646)
-  if (I->up_slot[matrixIndex] >= 0) I->up_src[I->up_slot[matrixIndex]] = (const double *)st; // last upload wins
-  else
-  {
-    I->up_slot[matrixIndex] = (int)I->up_idx.size();
-    I->up_idx.push_back(matrixIndex);
-    I->up_src.push_back((const double *)st);
-    I->up_shadow.push_back(-1);
-  }
-  if (!shadow.empty() && shadow[0] >= 0) { I->up_shadow[I->up_slot[matrixIndex]] = shadow[0]; ++I->n_up_shadow; }
-  if ((int)I->up_idx.size() >= 4 * kUploadBatch && (rc = flush_uploads(I))) return rc;
+  I->uploads.put(matrixIndex, (const double *)st); // last upload wins
+  if (!shadow.empty() && shadow[0] >= 0) I->uploads.want_snapshot(matrixIndex, shadow[0]);
+  if ((int)I->uploads.size() >= 4 * kUploadBatch && (rc = flush_uploads(I))) return rc;
   I_call.leave_queued_only(); // (a flush above -- flush_pmats, flush_uploads, also through the staging ring's rotation -- says so itself)
   return PHYHIP_SUCCESS;
 }
@@ -983,8 +968,7 @@ int phyhip_update_partials(int instance, const phyhip_operation *ops, int n, int
     }
     I->pending.push_back(DevOp{o.destinationPartials, o.child1Partials, o.child2Partials, o.child1TransitionMatrix,
                                o.child2TransitionMatrix, 0});
-    I->mat_in_queue[o.child1TransitionMatrix] = 1;
-    I->mat_in_queue[o.child2TransitionMatrix] = 1;
+    mark_matrix_readers(I, o.child1TransitionMatrix, o.child2TransitionMatrix);
   }
   I_call.leave_queued_only();
   return PHYHIP_SUCCESS;

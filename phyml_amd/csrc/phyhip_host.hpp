@@ -26,6 +26,9 @@
 //   phyhip_scan_plan.hpp the planning of the calls that run a list of candidates in chunks (the two regraft scans, Triple_Dist): chunk
 //                        size, the work-space layouts as data, the distinct-length slot table, record packing.  Plain host C++, no HIP
 //   phyhip_scan.hpp      their host driver: candidate checks, work-space reservation, the chunk walk, the scans' chunk loop
+//   phyhip_matrix_queue.hpp  the table of queued matrix refreshes (Instance::rebuilds, Instance::uploads: enqueue with the last
+//                        writer winning, snapshot slots, clear).  Plain host C++, no HIP; the command that took such a queue
+//                        along: SentCommand below
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
@@ -39,6 +42,7 @@
 #include "phyhip_aa.hpp"
 #include "phyhip_nt2.hpp"
 #include "phyhip_big.hpp"
+#include "phyhip_matrix_queue.hpp"
 
 #include <rccl/rccl.h>
 
@@ -265,6 +269,30 @@ struct Unstored
   Counters                        cnt_[4];
 };
 
+// The evaluation last handed to resident workgroups, kept until it is answered: what it was built from -- the operations, the
+// rebuilds it folded, the up to kArgUp host-computed matrices it carried (ResidentCtl::up_area).  Unanswered, it goes back into the
+// queue (requeue_sent, phyhip_queue.hip) and is launched.
+struct SentCommand
+{
+  std::vector<DevOp>  ops;
+  std::vector<int>    pm_idx;
+  std::vector<double> pm_len;
+  int                 n_up = 0;
+  int                 up_idx[kArgUp] = {0, 0, 0};
+  double              up_val[kArgUp][64];
+
+  void keep(const std::vector<DevOp> &pending, const MatrixTable<double> &rebuilds, const TreeParams &q)
+  {
+    ops = pending; pm_idx = rebuilds.idx(); pm_len = rebuilds.payload();
+    n_up = q.n_up; // (0, as it was, for a 20-state command: only nucleotide instances ever carry uploads -- plan_route)
+    for (int k = 0; k < q.n_up; ++k)
+    {
+      up_idx[k] = q.up_idx[k];
+      memcpy(up_val[k], q.up_val[k], sizeof up_val[k]);
+    }
+  }
+};
+
 struct Instance
 {
   Collective *co         = nullptr; // one-process-per-GPU mode: communicator attached by phyhip_comm_init_rank
@@ -347,13 +375,7 @@ struct Instance
   Resident    *r_inflight = nullptr;  // whose command the evaluation in flight is
   DlkParams    r_static;              // what the resident workgroups were launched with
   TreeParams   rt_static;
-  // the evaluation last handed to resident_nt2_kernel, kept until it is answered (unanswered: it is launched instead)
-  std::vector<DevOp>  rt_ops;
-  int                 rt_up_n = 0;      // ... and the host-computed matrices it carried (ResidentCtl::up_area)
-  int                 rt_up_idx[kArgUp] = {0, 0, 0};
-  double              rt_up_val[kArgUp][64];
-  std::vector<int>    rt_pm_idx;
-  std::vector<double> rt_pm_len;
+  SentCommand  sent;                  // the evaluation last handed to resident workgroups (unanswered: it is launched instead)
   bool         rt_skip = false;       // the evaluation being repeated after an unanswered command goes the ordinary way
   unsigned long long clean_epoch = 0, rt_epoch = 0; // times the stream was found finished after having run something; at the last command
   bool         touched_call = false;  // this entry-point call has put something on the stream
@@ -383,19 +405,14 @@ struct Instance
   bool                                   virt_inline = true; // (diag: PHYHIP_VIRT_INLINE=0 re-issues every virtual child as a step of its own)
   std::vector<InlineDef>                 pending_inl;        // per entry of `pending` as rewrite_pending left it (or empty: none has one)
   std::vector<std::vector<InlineDef>>    slot_inl;           // ... of the lists the device ring slots hold (content cache)
-  std::vector<int>                       pm_idx;    // queued device-side matrix rebuilds (index, edge length)
-  std::vector<double>                    pm_len;
-  std::vector<int>                       pm_slot;   // matrix index -> position in pm_idx, or -1
-  std::vector<int>                       pm_shadow; // per queued rebuild: slot that receives the matrix's OLD value first, or -1
-  int                                    n_pm_shadow = 0; // ... how many of them ask for one (such a list is rebuilt by pmat_kernel)
+  // The queued matrix refreshes (phyhip_matrix_queue.hpp).  The invariant between the two tables, kept by the two setters of
+  // phyhip.hip: a matrix is never queued in both, and a refresh of one kind lands before a later one of the other kind -- whoever
+  // queues a rebuild of a matrix with an upload pending flushes the uploads first, and the other way round.
+  MatrixTable<double>                    rebuilds;  // device-side rebuilds from an edge length (with snapshots: rebuilt by pmat_kernel)
+  MatrixTable<const double *>            uploads;   // host-computed matrices, their copies in pinned staging memory (with snapshots: upload_matrices_kernel)
+  std::vector<unsigned char>             mat_in_queue; // a queued operation reads this matrix (snapshot slots included): mark_matrix_readers / clear_matrix_readers below
   std::vector<std::vector<DevOp>>        slot_ops;  // what each device ring slot currently holds (content cache)
   std::vector<int>                       slot_kind; // 0 slim, 1 fat dist 1, 2 fat dist 2
-  std::vector<unsigned char>             mat_in_queue; // matrix index referenced by a queued op
-  std::vector<int>                       up_idx;       // host-computed matrices waiting for their upload launch
-  std::vector<const double *>            up_src;       // ... their copies in pinned staging memory
-  std::vector<int>                       up_slot;      // per matrix: position in up_idx or -1
-  std::vector<int>                       up_shadow;    // per queued upload: slot that receives the old value first, or -1
-  int                                    n_up_shadow = 0; // ... how many ask for one (such uploads go through upload_matrices_kernel)
   std::vector<uint32_t>                  masks;
   std::unordered_map<uint32_t, int>      mask_code;
   bool                                   masks_dirty = false;
@@ -457,6 +474,12 @@ static inline int make_current(int dev)
 }
 
 void big_release(Instance *I, bool restart_streak = true); // (phyhip_resident.hip)
+
+// "a queued operation reads matrix m" (a refresh of such a matrix launches the queue first): an operation's two matrices; the queue was launched
+inline void mark_matrix_readers(Instance *I, int pm1, int pm2) { I->mat_in_queue[pm1] = 1; I->mat_in_queue[pm2] = 1; }
+inline void clear_matrix_readers(Instance *I) { std::fill(I->mat_in_queue.begin(), I->mat_in_queue.end(), 0); }
+// no refresh of matrix m is queued, in either table
+inline bool no_refresh_queued(const Instance *I, int m) { return !I->rebuilds.queued(m) && !I->uploads.queued(m); }
 
 // ---- the instance table and THE choke point of the resident protocol -------------------------------
 // Resident workgroups are not ordered with the instance's stream, so they may only be used while nothing queued on it is still

@@ -9,30 +9,27 @@ namespace phyhip_host
 // Host-computed matrices queued by phyhip_set_transition_matrix: one launch per kUploadBatch of them.
 int flush_uploads(Instance *I)
 {
-  if (!I->up_idx.empty())
+  const auto &up = I->uploads;
+  if (!up.empty())
   { // (the upload kernel writes the matrix table: behind the exit of the large-grid resident workgroups, whose own rebuilt
     // matrices sit in their L2s until they leave -- reachable from entry points that keep them, phyhip.hip)
     big_release(I);
     I->touched_call = true;
   }
   size_t done = 0;
-  while (done < I->up_idx.size())
+  while (done < up.size())
   {
-    const int n = (int)std::min<size_t>(I->up_idx.size() - done, kUploadBatch);
+    const int n = (int)std::min<size_t>(up.size() - done, kUploadBatch);
     MatUploadParams q;
     memset(&q, 0, sizeof q);
     q.count = n; q.S = I->S; q.C = I->C; q.pmats = I->d_pmats; q.afrag = I->perm ? I->d_afrag : nullptr;
     for (int k = 0; k < kUploadBatch; ++k) q.shadow[k] = -1;
-    for (int k = 0; k < n; ++k) { q.idx[k] = I->up_idx[done + k]; q.src[k] = I->up_src[done + k]; q.shadow[k] = I->up_shadow[done + k]; }
+    for (int k = 0; k < n; ++k) { q.idx[k] = up.idx()[done + k]; q.src[k] = up.payload()[done + k]; q.shadow[k] = up.snapshot()[done + k]; }
     hipLaunchKernelGGL(upload_matrices_kernel, dim3(n), dim3(256), q.afrag ? sizeof(double) * (size_t)I->C * I->S * I->S : 0, I->stream, q);
     HIPCHK(hipGetLastError());
     done += n;
   }
-  for (int m : I->up_idx) I->up_slot[m] = -1;
-  I->up_idx.clear();
-  I->up_src.clear();
-  I->up_shadow.clear();
-  I->n_up_shadow = 0;
+  I->uploads.clear();
   return 0;
 }
 
@@ -42,8 +39,9 @@ int flush_pmats(Instance *I)
   big_release(I);
   I->touched_call = true;
   int done = 0, rc = 0;
-  if (!I->up_idx.empty() && (rc = flush_uploads(I))) return rc;
-  const int count = (int)I->pm_idx.size();
+  if (!I->uploads.empty() && (rc = flush_uploads(I))) return rc;
+  const auto &pm = I->rebuilds;
+  const int   count = (int)pm.size();
   while (done < count)
   {
     const int  n     = std::min(count - done, I->pm_scratch_cap);
@@ -55,21 +53,21 @@ int flush_pmats(Instance *I)
       for (int k = 0; k < kSmallPm; ++k) q.small_shadow[k] = -1;
       for (int k = 0; k < n; ++k)
       {
-        q.small_idx[k] = I->pm_idx[done + k];
-        q.small_len[k] = I->pm_len[done + k];
-        q.small_shadow[k] = I->pm_shadow[done + k];
+        q.small_idx[k] = pm.idx()[done + k];
+        q.small_len[k] = pm.payload()[done + k];
+        q.small_shadow[k] = pm.snapshot()[done + k];
       }
     }
     else
     {
       void        *st = nullptr;
-      const bool   sh = I->n_pm_shadow > 0; // (snapshots of old values for virtual buffers: a third array)
+      const bool   sh = pm.snapshots() > 0; // (snapshots of old values for virtual buffers: a third array)
       const size_t bi = (sizeof(int) * n + 15) & ~size_t(15), bl = sizeof(double) * n;
       rc = I->ring.alloc(bi + bl + (sh ? bi : 0), I->stream, &st);
       if (rc) return rc;
-      memcpy(st, I->pm_idx.data() + done, sizeof(int) * n);
-      memcpy((char *)st + bi, I->pm_len.data() + done, bl);
-      if (sh) memcpy((char *)st + bi + bl, I->pm_shadow.data() + done, sizeof(int) * n);
+      memcpy(st, pm.idx().data() + done, sizeof(int) * n);
+      memcpy((char *)st + bi, pm.payload().data() + done, bl);
+      if (sh) memcpy((char *)st + bi + bl, pm.snapshot().data() + done, sizeof(int) * n);
       if (I->pm_copy)
       {
         HIPCHK(hipMemcpyAsync(I->d_pmscratch, st, bi + bl, hipMemcpyHostToDevice, I->stream));
@@ -110,11 +108,7 @@ int flush_pmats(Instance *I)
     HIPCHK(hipGetLastError());
     done += n;
   }
-  for (int m : I->pm_idx) I->pm_slot[m] = -1;
-  I->pm_idx.clear();
-  I->pm_len.clear();
-  I->pm_shadow.clear();
-  I->n_pm_shadow = 0;
+  I->rebuilds.clear();
   return 0;
 }
 
@@ -191,16 +185,12 @@ static bool stream_clean_for_resident(Instance *I)
 // The queue is in the stream (or in a resident command): forget it.  Matrix rebuilds that rode with the evaluation go with it.
 static void retire_queue(Instance *I, bool fold_pm)
 {
-  if (fold_pm)
-  {
-    for (int m : I->pm_idx) I->pm_slot[m] = -1;
-    I->pm_idx.clear();
-    I->pm_len.clear();
-    I->pm_shadow.clear();
-  }
+  // (no snapshot is lost with them: plan_route sets fold_pm only where rebuilds.snapshots() == 0 -- the aa_take condition and the
+  // nucleotide condition both say so)
+  if (fold_pm) I->rebuilds.clear();
   I->pending.clear();
   I->unstored.n_front = 0;
-  std::fill(I->mat_in_queue.begin(), I->mat_in_queue.end(), 0);
+  clear_matrix_readers(I);
 }
 
 // Which of the five routes takes the call: an ordinary launch, the short-launch resident evaluator (decided later, once the
@@ -215,15 +205,15 @@ static int plan_route(Instance *I, const EdgeEval *ee, FlushPlan &f)
   static const int fold_grid_max = diag_env("PHYHIP_FOLD_GRID") ? atoi(diag_env("PHYHIP_FOLD_GRID")) : 512;
   // a short list of HOST-computed matrices rides in the arguments of the lane-per-pattern nucleotide kernel at every grid size
   // (TreeParams::n_up): no upload kernel in front of the traversal
-  f.up_ride = I->soa && I->arg_uploads && !I->up_idx.empty() && (int)I->up_idx.size() <= kArgUp && I->pm_idx.empty() &&
-              (n_ops > 0 || ee) && I->C <= 4 && !I->class_axis && !(I->ablate & 8) && I->n_up_shadow == 0;
+  f.up_ride = I->soa && I->arg_uploads && !I->uploads.empty() && (int)I->uploads.size() <= kArgUp && I->rebuilds.empty() &&
+              (n_ops > 0 || ee) && I->C <= 4 && !I->class_axis && !(I->ablate & 8) && I->uploads.snapshots() == 0;
   // large grids: an evaluation the large-grid resident workgroups can take (phyhip_big.hpp) carries its matrices in the command
   // (host-computed matrices -- the bit-exact route -- stay with the one-wave launch that takes them in its arguments: the
   // large-grid kernel launched with them in ITS arguments was measured, 30-31 against 28.4 us per candidate at 500 x 100 000)
   const bool big_form0 = ee && (ee->eigen || (ee->to_host && !ee->dev_out)) && n_ops <= 2 && I->args_recs && I->fold_pmats &&
-                         (int)I->pm_idx.size() <= 4 && !I->rt_skip; // (an evaluation that kernel can take)
-  const bool big_form = big_form0 && I->up_idx.empty();
-  f.big_fit = big_form0 && (I->up_idx.empty() || up_resident(I, f, I->rb)) && big_eligible(I) && !I->prof;
+                         (int)I->rebuilds.size() <= 4 && !I->rt_skip; // (an evaluation that kernel can take)
+  const bool big_form = big_form0 && I->uploads.empty();
+  f.big_fit = big_form0 && (I->uploads.empty() || up_resident(I, f, I->rb)) && big_eligible(I) && !I->prof;
   f.big_try = f.big_fit && big_ready(I);
   // ... and they are there (or launched now): decided before the records are built -- a resident command of two operations runs
   // them one after the other per tile, without register forwarding between them (phyhip_big.hpp)
@@ -231,7 +221,7 @@ static int plan_route(Instance *I, const EdgeEval *ee, FlushPlan &f)
   {
     const int brc = big_ensure(I);
     if (brc < 0) return brc;
-    f.big_take = brc == 0 && (I->up_idx.empty() || up_resident(I, f, I->rb)); // (a record that turned out to live in host memory: launch)
+    f.big_take = brc == 0 && (I->uploads.empty() || up_resident(I, f, I->rb)); // (a record that turned out to live in host memory: launch)
   }
   // ... or they are not, and the same kernel is LAUNCHED for this one evaluation (BigArgs::n_one_shot) instead of pmat_kernel +
   // a traversal of one-wave workgroups + a record per workgroup: where the final sum can run through one partial sum per
@@ -240,18 +230,18 @@ static int plan_route(Instance *I, const EdgeEval *ee, FlushPlan &f)
                big_sum_by_group(I, I->grid_nt2);
   if (kDiag && ee && getenv("PHYHIP_RESIDENT_DEBUG") && big_shape(I))
     fprintf(stderr, "big: fit %d try %d | eligible %d ops %d pm %zu up %zu prof %d skip %d | dirty_prev %d touched %d clean_after %llu stamp %llu streak %d launched %d owner %p me %p\n",
-            (int)f.big_fit, (int)f.big_try, (int)big_eligible(I), n_ops, I->pm_idx.size(), I->up_idx.size(), (int)I->prof, (int)I->rt_skip, (int)I->dirty_prev,
+            (int)f.big_fit, (int)f.big_try, (int)big_eligible(I), n_ops, I->rebuilds.size(), I->uploads.size(), (int)I->prof, (int)I->rt_skip, (int)I->dirty_prev,
             (int)I->touched_call, I->clean_after, *reinterpret_cast<volatile unsigned long long *>(I->h_result + 3), I->big_streak, (int)I->rb.launched,
             (void *)g_big_owner[I->dev < 64 ? I->dev : 0].load(), (void *)I);
   // small 20-state alignments: an evaluation the resident workgroups of traverse_aa_kernel<..., RES> can take -- decided here, before
   // the matrix queue is dealt with, because they rebuild the queued matrices themselves (a launched 20-state kernel cannot: without
   // them the rebuild is pmat20_kernel's launch in front)
   if (resident_aa_eligible(I) && ee && !ee->eigen && ee->to_host && !ee->dev_out && n_ops <= 2 && I->args_recs && I->fold_pmats &&
-      (int)I->pm_idx.size() <= 4 && I->up_idx.empty() && I->n_pm_shadow == 0 && !I->prof && !I->rt_skip)
+      (int)I->rebuilds.size() <= 4 && I->uploads.empty() && I->rebuilds.snapshots() == 0 && !I->prof && !I->rt_skip)
   {
     // (a rebuilt matrix the command does not read goes through the ring's spare item: two tables)
     int unread = 0;
-    for (int m : I->pm_idx)
+    for (int m : I->rebuilds.idx())
     {
       bool read = m == ee->pm;
       for (const DevOp &o : I->pending) read = read || o.pm1 == m || o.pm2 == m;
@@ -260,9 +250,9 @@ static int plan_route(Instance *I, const EdgeEval *ee, FlushPlan &f)
     if (unread > 2) ++I->rt.n_busy;
     else f.aa_take = stream_clean_for_resident(I);
   }
-  f.fold_pm = (f.aa_take && !I->pm_idx.empty()) ||
-              (I->soa && I->fold_pmats && (I->grid_nt2 <= fold_grid_max || f.big_try || f.one_shot) && !I->pm_idx.empty() && (int)I->pm_idx.size() <= 8 &&
-               I->up_idx.empty() && (n_ops > 0 || ee) && I->C <= 4 && !I->class_axis && !(I->ablate & 8) && I->n_pm_shadow == 0);
+  f.fold_pm = (f.aa_take && !I->rebuilds.empty()) ||
+              (I->soa && I->fold_pmats && (I->grid_nt2 <= fold_grid_max || f.big_try || f.one_shot) && !I->rebuilds.empty() && (int)I->rebuilds.size() <= 8 &&
+               I->uploads.empty() && (n_ops > 0 || ee) && I->C <= 4 && !I->class_axis && !(I->ablate & 8) && I->rebuilds.snapshots() == 0);
   return 0;
 }
 
@@ -271,22 +261,19 @@ static void fill_matrix_args(Instance *I, const FlushPlan &f, TreeParams &q)
 {
   if (f.up_ride)
   {
-    q.n_up = (int)I->up_idx.size();
+    q.n_up = (int)I->uploads.size();
     for (int k = 0; k < q.n_up; ++k)
     {
-      q.up_idx[k] = I->up_idx[k];
-      memcpy(q.up_val[k], I->up_src[k], sizeof(double) * 16 * I->C); // (pinned staging memory: an ordinary host read)
+      q.up_idx[k] = I->uploads.idx()[k];
+      memcpy(q.up_val[k], I->uploads.payload()[k], sizeof(double) * 16 * I->C); // (pinned staging memory: an ordinary host read)
     }
     q.pmats_rw = I->d_pmats;
-    for (int m : I->up_idx) I->up_slot[m] = -1;
-    I->up_idx.clear();
-    I->up_src.clear();
-    I->up_shadow.clear();
+    I->uploads.clear(); // (no snapshot is lost with them: plan_route sets up_ride only where uploads.snapshots() == 0)
   }
   if (f.fold_pm)
   {
-    q.n_fresh = (int)I->pm_idx.size();
-    for (int k = 0; k < q.n_fresh; ++k) { q.fresh_idx[k] = I->pm_idx[k]; q.fresh_len[k] = I->pm_len[k]; }
+    q.n_fresh = (int)I->rebuilds.size();
+    for (int k = 0; k < q.n_fresh; ++k) { q.fresh_idx[k] = I->rebuilds.idx()[k]; q.fresh_len[k] = I->rebuilds.payload()[k]; }
     // (4 states, one eigen system, <= 4 categories: see fold_pm) the eigen system rides in the arguments as well
     if (I->S == 4)
     {
@@ -549,13 +536,7 @@ static void pack_command(unsigned long long *words, int n_words, const TreeParam
 // is kept until the answer is in: an evaluation nobody answers is launched the ordinary way (flush_and_wait)
 static void send_command(Instance *I, Resident &R, const TreeParams &q, const unsigned long long *words, int n_words)
 {
-  I->rt_ops = I->pending; I->rt_pm_idx = I->pm_idx; I->rt_pm_len = I->pm_len;
-  I->rt_up_n = q.n_up; // (0, as it was, for a 20-state command: only nucleotide instances ever carry uploads -- plan_route)
-  for (int k = 0; k < q.n_up; ++k)
-  {
-    I->rt_up_idx[k] = q.up_idx[k];
-    memcpy(I->rt_up_val[k], q.up_val[k], sizeof(double) * 64);
-  }
+  I->sent.keep(I->pending, I->rebuilds, q);
   resident_send(I, R, words, n_words); // (every sector the workgroups wait for carries the command's number)
   I->rt_epoch = I->clean_epoch;
 }
@@ -986,10 +967,10 @@ static int flush_impl(Instance *I, const EdgeEval *ee)
   I->unstored.keep_clear();
   const int n_ops = f.n_ops = (int)I->pending.size();
   int       rc = 0;
-  if (n_ops > 0 || ee || !I->pm_idx.empty() || !I->up_idx.empty()) I->stream_dirty = true;
+  if (n_ops > 0 || ee || !I->rebuilds.empty() || !I->uploads.empty()) I->stream_dirty = true;
   if (ee) I->fenced_eval = false;
   if ((rc = plan_route(I, ee, f))) return rc;
-  if (!f.fold_pm && !f.up_ride && (!I->pm_idx.empty() || !I->up_idx.empty()) && (rc = flush_pmats(I))) return rc;
+  if (!f.fold_pm && !f.up_ride && (!I->rebuilds.empty() || !I->uploads.empty()) && (rc = flush_pmats(I))) return rc;
   if (n_ops == 0 && !ee) return 0;
   if ((rc = upload_masks(I))) return rc;
 
@@ -1220,6 +1201,26 @@ int collect_profile(Instance *I)
   return 0;
 }
 
+// The command nobody answered, back into the queue: its operations (and the matrices they read), the rebuilds it folded unless
+// the matrix has been queued since, then its host-computed matrices as phyhip_set_transition_matrix queued them
+static int requeue_sent(Instance *I)
+{
+  SentCommand &c = I->sent;
+  I->pending = c.ops;
+  for (const DevOp &o : I->pending) mark_matrix_readers(I, o.pm1, o.pm2);
+  for (size_t k = 0; k < c.pm_idx.size(); ++k) I->rebuilds.put_if_absent(c.pm_idx[k], c.pm_len[k]);
+  for (int k = 0; k < c.n_up; ++k)
+  {
+    const size_t bytes = (size_t)I->C * I->S * I->S * sizeof(double);
+    void        *st = nullptr;
+    if (int rc = I->ring.alloc(bytes, I->stream, &st)) return rc;
+    memcpy(st, c.up_val[k], bytes);
+    I->uploads.put_if_absent(c.up_idx[k], (const double *)st); // (absent: the command took every queued upload)
+  }
+  c.n_up = 0;
+  return 0;
+}
+
 // An evaluation the host waits for (edge sum, or the empty records of a small alignment's Update_Eigen_Lr): queue, launch or
 // hand to the resident short-launch evaluator, wait.  An evaluation the resident workgroups do not answer is launched.
 int flush_and_wait(Instance *I, EdgeEval &ee, bool flushed)
@@ -1236,30 +1237,7 @@ int flush_and_wait(Instance *I, EdgeEval &ee, bool flushed)
     resident_stop(*by);
     if (by == &I->rb) big_release(I);
     I->r_inflight = nullptr; I->host_sum_n = 0;
-    I->pending = I->rt_ops;
-    for (const DevOp &o : I->pending) { I->mat_in_queue[o.pm1] = 1; I->mat_in_queue[o.pm2] = 1; }
-    for (size_t k = 0; k < I->rt_pm_idx.size(); ++k)
-      if (I->pm_slot[I->rt_pm_idx[k]] < 0)
-      {
-        I->pm_slot[I->rt_pm_idx[k]] = (int)I->pm_idx.size();
-        I->pm_idx.push_back(I->rt_pm_idx[k]);
-        I->pm_len.push_back(I->rt_pm_len[k]);
-        I->pm_shadow.push_back(-1);
-      }
-    for (int k = 0; k < I->rt_up_n; ++k)
-    { // ... and its host-computed matrices: queued again as phyhip_set_transition_matrix queued them
-      const int    m = I->rt_up_idx[k];
-      const size_t bytes = (size_t)I->C * I->S * I->S * sizeof(double);
-      void        *st = nullptr;
-      if ((rc = I->ring.alloc(bytes, I->stream, &st))) return rc;
-      memcpy(st, I->rt_up_val[k], bytes);
-      if (I->up_slot[m] >= 0) continue; // (cannot be: the command took every queued upload)
-      I->up_slot[m] = (int)I->up_idx.size();
-      I->up_idx.push_back(m);
-      I->up_src.push_back((const double *)st);
-      I->up_shadow.push_back(-1);
-    }
-    I->rt_up_n = 0;
+    if ((rc = requeue_sent(I))) return rc;
     I->rt_skip = true;
     rc = flush(I, &ee);
     I->rt_skip = false;

@@ -36,7 +36,7 @@ static void store_definition(Instance *I, int buf)
   while (at < (size_t)u.n_front && u.seq(I->pending[at].dest) < u.seq(buf)) ++at;
   ++u.n_front;
   I->pending.insert(I->pending.begin() + (long)at, op);
-  I->mat_in_queue[op.pm1] = 1; I->mat_in_queue[op.pm2] = 1;
+  mark_matrix_readers(I, op.pm1, op.pm2);
   u.end(buf, U::kMaterial);
 }
 
@@ -250,7 +250,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
   auto before_read = [&](int c, DevOp &reader, InlineDef &rin, int bit) {
     if (!is_virtual(c)) return;
     DevOp d = u.def(c);
-    I->mat_in_queue[d.pm1] = 1; I->mat_in_queue[d.pm2] = 1;
+    mark_matrix_readers(I, d.pm1, d.pm2);
     ++u.n_recomputed;
     if (in_step && rin.a < 0 && reader.c1 != reader.c2)
     {
@@ -281,7 +281,7 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
     if (!is_virtual(b)) return;
     const DevOp d = u.def(b);
     u.end(b, U::kMaterial);
-    I->mat_in_queue[d.pm1] = 1; I->mat_in_queue[d.pm2] = 1;
+    mark_matrix_readers(I, d.pm1, d.pm2);
     L.push_back(d); LI.push_back(none);
   };
   for (int b : u.keep_real) store_now(b);
