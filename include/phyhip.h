@@ -635,6 +635,13 @@ int phyhip_set_chained_buffers(int instance, int minOperations);
    instances: the first shard's counters. */
 int phyhip_get_chained_stats(int instance, long long out[4]);
 
+/* The operation records of the nucleotide list-form launches (4 states, up to 4 categories): out[0] lists built in the compact
+   form, out[1] list-form launches that found their list in a device slot and built nothing.  Then, over the lists built, how an
+   operation's child reaches its step -- out[2 + 5 * s + k], s = 0 / 1 the first / second child, k = 0 a tip row, 1 computed in the
+   step (a virtual tip x tip result), 2 / 3 forwarded in registers from the previous / second-previous operation, 4 loaded from
+   its buffer -- padding records of odd lists included.  Sharded instances: the first shard's counters. */
+int phyhip_get_record_stats(int instance, long long out[12]);
+
 /* ---- parsimony (src/pars.c) --------------------------------------------------------------------------------------------------- */
 
 /* Update_Partial_Pars (src/pars.c:239-393) and Pars / Pars_Core (src/pars.c:20-52, 397-437) on the device, in the reference's own

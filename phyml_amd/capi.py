@@ -71,7 +71,7 @@ SYMBOLS = [
     "phyhip_calculate_eigen_lnl_dlnl", "phyhip_calculate_eigen_lnl", "phyhip_get_dot_prod", "phyhip_set_stream",
     "phyhip_synchronize", "phyhip_profile", "phyhip_profile_read", "phyhip_calculate_mixture_log_likelihood",
     "phyhip_calculate_mixture_eigen_lnl_dlnl", "phyhip_comm_get_unique_id", "phyhip_comm_init_rank", "phyhip_comm_size",
-    "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_get_deferred_stats", "phyhip_set_chained_buffers", "phyhip_get_chained_stats", "phyhip_calculate_class_mixture_log_likelihood",
+    "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_get_deferred_stats", "phyhip_set_chained_buffers", "phyhip_get_chained_stats", "phyhip_get_record_stats", "phyhip_calculate_class_mixture_log_likelihood",
     "phyhip_calculate_class_mixture_eigen_lnl_dlnl", "phyhip_get_class_scale_factors", "phyhip_set_mixture_invariant_sites",
     "phyhip_calculate_edge_site_outputs_exact", "phyhip_calculate_node_state_posteriors", "phyhip_profile_read_node_posteriors",
     "phyhip_calculate_pairwise_ml_distances", "phyhip_set_pairwise_work_space", "phyhip_profile_read_pairwise",
@@ -727,6 +727,13 @@ class Instance:
         """(buffers chained now, stores left out, definitions stored on demand, definitions dropped)"""
         out = (C.c_longlong * 4)()
         _chk(self.L.phyhip_get_chained_stats(self.id, out))
+        return tuple(int(v) for v in out)
+
+    def record_stats(self):
+        """phyhip_get_record_stats: (compact lists built, launches served from a device slot, then per child position five counts:
+        tip, in-step, forwarded k-1, forwarded k-2, loaded)"""
+        out = (C.c_longlong * 12)()
+        _chk(self.L.phyhip_get_record_stats(self.id, out))
         return tuple(int(v) for v in out)
 
     def profile_read_eigen(self):

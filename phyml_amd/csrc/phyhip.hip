@@ -1346,6 +1346,14 @@ int phyhip_get_chained_stats(int instance, long long out[4])
   return PHYHIP_SUCCESS;
 }
 
+int phyhip_get_record_stats(int instance, long long out[12])
+{
+  if (Group *G = get_group(instance)) return phyhip_get_record_stats(G->sub_id[0], out);
+  GET_INST(I, instance);
+  memcpy(out, I->rec_stats, sizeof I->rec_stats);
+  return PHYHIP_SUCCESS;
+}
+
 int phyhip_profile_read_collective(int instance, double *outMs, int *outCount, int *outRanks)
 {
   Group *G = get_group(instance);

@@ -395,9 +395,10 @@ struct Instance
   bool      host_sum   = true;    // PHYHIP_HOST_SUM=0: large grids use final_reduce_kernel instead
   void     *d_pmscratch = nullptr; // [pm_scratch_cap] ints + doubles for phyhip_update_transition_matrices
   int       pm_scratch_cap = 0;
-  char     *d_ops      = nullptr; // ring of op lists on the device (slim DevOp or fat IssueRec+ExecRec)
+  char     *d_ops      = nullptr; // ring of op lists on the device (slim DevOp, fat IssueRec+ExecRec, or compact NtIssue+NtExec)
   size_t    ops_slot_bytes = 0;
   int       ops_cap = 0, ops_slots = 4, ops_slot = 0;
+  long long rec_stats[12] = {0};  // phyhip_get_record_stats
   int       grid = 0, grid_nt = 0, block_nt = 64;
 
   std::vector<DevOp>                     pending;

@@ -102,6 +102,37 @@ enum : unsigned
   kOpCh1 = 64u, kOpCh2 = 128u
 };
 
+// Compact records of the lane-per-pattern nucleotide kernel's LIST form (nt2_run with ARGS == 0, phyhip_nt2.hpp; built by
+// fill_compact_records, phyhip_queue.hip).  The partials, the scale vectors and the tip rows are one allocation each, so a child or
+// a destination is a 32-bit offset in 16-byte units from its arena's base (64 GiB of reach) and a buffer descriptor is formed on
+// the device only where a load or a store is live; the descriptors' size and flags words are the same for every operation.  A
+// step keeps 8 + 4 words of the operation it loads for and 4 of the one it computes, instead of 24 and 8.  The list-form kernels
+// keep their argument types (their names are pinned): the device slot is read through the IssueRec / ExecRec pointers as arrays
+// of these two structs -- nothing else reads a slot of this kind (its slot_kind says so).
+struct alignas(32) NtIssue
+{
+  unsigned fl;      // kRec* bits; bits 8-31: the second tip of the in-step child (its index)
+  unsigned pm[2];   // byte offsets of the operation's two matrices inside the matrix table
+  unsigned data[2]; // child data: offset from the partials arena (live loads only); the in-step child's slot: byte offset of ITS first matrix
+  unsigned aux[2];  // the child's one auxiliary dword: offset of its scale vector, or (kRecT*) of its tip row -- an in-step child's first tip
+  unsigned pmx;     // byte offset of the in-step child's second matrix
+};
+struct alignas(16) NtExec
+{
+  unsigned fl;        // kOp* bits | kRecStore
+  unsigned dst_data;  // offset of the destination from the partials arena
+  unsigned dst_scale; // ... of its scale vector from the scales arena
+  unsigned pad;
+};
+enum : unsigned
+{
+  kRecL1 = 1u, kRecL2 = 2u,   // NtIssue::fl: the data of child 1 / child 2 is loaded
+  kRecA1 = 4u, kRecA2 = 8u,   // its auxiliary dword is loaded ...
+  kRecT1 = 16u, kRecT2 = 32u, // ... from a tip row (else from a scale vector)
+  kRecIn1 = 64u, kRecIn2 = 128u, // child 1 / child 2 is computed in the step (kOpCh1 / kOpCh2)
+  kRecStore = 256u            // NtExec::fl: the result is stored (else the step issues no store)
+};
+
 // Everything a traversal launch needs.  Passed by value (fits the 4 KiB kernarg segment easily).
 struct TreeParams
 {

@@ -19,7 +19,9 @@
 // Everything else is the pipeline of traverse_nt_kernel: host-prepared buffer descriptors (size 0 = dead load: not
 // issued, the test is a scalar branch), loads of operation k+2 in flight while k is computed, results of
 // the last two operations forwarded in registers (two alternating register files, no copies), both
-// transition matrices of an operation staged once per wave into LDS and read back as broadcasts.
+// transition matrices of an operation staged once per wave into LDS and read back as broadcasts.  The list form (ARGS == 0) reads
+// compact records -- flag bits and 32-bit offsets from the three arenas, NtIssue / NtExec in phyhip_kernels.hpp -- and forms a
+// descriptor only for a load or a store that is live; the short forms read the descriptors themselves.
 #pragma once
 #ifndef PHYHIP_LOAD_AUX
 #define PHYHIP_LOAD_AUX 2 // cache policy bits of the children loads: non-temporal too (read once: -1 ... -3 % on the large cases)
@@ -147,15 +149,51 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
   };
 
   // issue the loads an operation needs.  Which ones are live was decided by the host: a child that is a tip, forwarded in
-  // registers or computed in the step (in-step) has a data descriptor of size 0, a forwarded child a scale descriptor of size 0.
-  // Dead loads are not issued at all (the tests are on wave-uniform record words, so they are scalar branches): a 64-lane load
+  // registers or computed in the step (in-step) has a data descriptor of size 0, a forwarded child a scale descriptor of size 0
+  // (compact records: the kRecL* / kRecA* bits say the same).  Dead loads are not issued at all (the tests are on wave-uniform record words, so they are scalar branches): a 64-lane load
   // through a size-0 descriptor still takes a vector-memory issue slot and its address processing, and on this path the
   // per-CU vector-memory instruction rate is the limit.  Registers of a load not issued keep an older operation's value;
   // the step reads them only for the children that were loaded.  List form only: a launch or command of one or two operations
   // (ARGS) is a chain of dependent round trips, and the branches in front of its first loads made the large-grid SPR candidate
   // slower (24.1 -> 25.4 us), so the short forms issue every load as before.
   constexpr bool all = ARGS != 0;
-  auto issue_data = [&](const IssueRec &o, Raw &r) {
+  // List form: compact records (NtIssue / NtExec, phyhip_kernels.hpp) read through the record pointers.  A descriptor is the
+  // arena's base + (offset << 4) and one of three loop-invariant sizes -- one buffer's bytes, as the host-made descriptors had.
+  constexpr bool compact = ARGS == 0;
+  using IRec = typename std::conditional<compact, NtIssue, IssueRec>::type;
+  using XRec = typename std::conditional<compact, NtExec, ExecRec>::type;
+  const unsigned data_bytes = (unsigned)q.Ppad * (unsigned)(C * S * 8), scale_bytes = (unsigned)q.Ppad * (cls ? 4u * C : 4u), tip_bytes = (unsigned)q.Ppad;
+  auto arena = [&](const void *base, unsigned off16, unsigned bytes) {
+    const unsigned long long a = (unsigned long long)reinterpret_cast<uintptr_t>(base) + ((unsigned long long)uni(off16) << 4);
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(a), 0, (int)bytes, 0x00020000);
+  };
+  auto compact_data = [&](const NtIssue &o, Raw &r) {
+    const unsigned f = uni(o.fl);
+    if (f & kRecL1)
+    {
+      const __amdgpu_buffer_rsrc_t d1r = arena(q.partials, o.data[0], data_bytes);
+#pragma unroll
+      for (int e = 0; e < HP; ++e) r.a[e] = __builtin_amdgcn_raw_buffer_load_b128(d1r, voff16, (unsigned)e * rowb, PHYHIP_LOAD_AUX);
+    }
+    if (f & kRecL2)
+    {
+      const __amdgpu_buffer_rsrc_t d2r = arena(q.partials, o.data[1], data_bytes);
+#pragma unroll
+      for (int e = 0; e < HP; ++e) r.b[e] = __builtin_amdgcn_raw_buffer_load_b128(d2r, voff16, (unsigned)e * rowb, PHYHIP_LOAD_AUX);
+    }
+    // one auxiliary dword per child: its scale exponent, or the aligned dword of its tip row that holds its state byte
+    auto aux = [&](const bool tip, const unsigned off16) {
+      const void *base = tip ? (const void *)tip_codes : (const void *)q.scales;
+      return __builtin_amdgcn_raw_buffer_load_b32(arena(base, off16, tip ? tip_bytes : scale_bytes), tip ? (p & ~3u) : voff4, 0, 0);
+    };
+    if (f & kRecA1) r.sa = aux((f & kRecT1) != 0, o.aux[0]);
+    if (f & kRecA2) r.sb = aux((f & kRecT2) != 0, o.aux[1]);
+    if constexpr (INL)
+    { // the in-step child's second tip row (only an operation with such a child has one)
+      if (f & (kRecIn1 | kRecIn2)) r.tx = __builtin_amdgcn_raw_buffer_load_b32(arena(tip_codes, (f >> 8) * (tip_bytes >> 4), tip_bytes), p & ~3u, 0, 0);
+    }
+  };
+  auto desc_data = [&](const IssueRec &o, Raw &r) {
     // one auxiliary dword per child: a tip child has no scale vector and an internal child no tip byte, so the host
     // points the same descriptor at whichever row exists (spare word x = 1: tip row, addressed by aligned dword)
     if (all || uni(o.c1_data.bytes))
@@ -183,7 +221,26 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       }
     }
   };
-  auto issue_pm = [&](const IssueRec &o, u32x4 &pc, u32x4 &pc2) {
+  auto issue_data = [&](const IRec &o, Raw &r) {
+    if constexpr (compact) compact_data(o, r);
+    else desc_data(o, r);
+  };
+  auto compact_pm = [&](const NtIssue &o, u32x4 &pc, u32x4 &pc2) {
+    // this lane's 16-byte piece of [matrix 1 | matrix 2] (C*16 doubles each)
+    int ch = (lane < 16 * C) ? lane : 0;
+    const int      mat = ch / (8 * C), within = ch - mat * 8 * C;
+    pc = __builtin_amdgcn_raw_buffer_load_b128(pm_rsrc, (mat ? uni(o.pm[1]) : uni(o.pm[0])) + (unsigned)within * 16u, 0, 0);
+    if constexpr (INL)
+    { // ... and of the in-step child's two matrices (only when there is such a child: otherwise staged from stale registers, never read)
+      const unsigned f = uni(o.fl);
+      if (f & (kRecIn1 | kRecIn2))
+      {
+        const unsigned first = (f & kRecIn2) ? uni(o.data[1]) : uni(o.data[0]);
+        pc2 = __builtin_amdgcn_raw_buffer_load_b128(pm_rsrc, (mat ? uni(o.pmx) : first) + (unsigned)within * 16u, 0, 0);
+      }
+    }
+  };
+  auto desc_pm = [&](const IssueRec &o, u32x4 &pc, u32x4 &pc2) {
     // this lane's 16-byte piece of [matrix 1 | matrix 2] (C*16 doubles each)
     int ch = (lane < 16 * C) ? lane : 0;
     const int      mat = ch / (8 * C), within = ch - mat * 8 * C;
@@ -200,7 +257,11 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       }
     }
   };
-  auto issue = [&](const IssueRec &o, Raw &r, u32x4 &pc, u32x4 &pc2) {
+  auto issue_pm = [&](const IRec &o, u32x4 &pc, u32x4 &pc2) {
+    if constexpr (compact) compact_pm(o, pc, pc2);
+    else desc_pm(o, pc, pc2);
+  };
+  auto issue = [&](const IRec &o, Raw &r, u32x4 &pc, u32x4 &pc2) {
     issue_data(o, r);
     issue_pm(o, pc, pc2);
   };
@@ -275,12 +336,14 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
   constexpr bool early = !all && DIST == 2;
 
   // records: device slot ring, or the kernel arguments for launches of one or two operations (last <= 1)
-  auto IR = [&](int i) -> IssueRec {
-    if constexpr (ARGS != 0 && !LREC) return i ? q.arg_ir[1] : q.arg_ir[0];
+  auto IR = [&](int i) -> IRec {
+    if constexpr (compact) return reinterpret_cast<const NtIssue *>(irec)[i];
+    else if constexpr (ARGS != 0 && !LREC) return i ? q.arg_ir[1] : q.arg_ir[0];
     else return irec[i];
   };
-  auto XR = [&](int i) -> ExecRec {
-    if constexpr (ARGS != 0 && !LREC) return i ? q.arg_xr[1] : q.arg_xr[0];
+  auto XR = [&](int i) -> XRec {
+    if constexpr (compact) return reinterpret_cast<const NtExec *>(xrec)[i];
+    else if constexpr (ARGS != 0 && !LREC) return i ? q.arg_xr[1] : q.arg_xr[0];
     else return xrec[i];
   };
   const int last = ARGS ? 1 : q.n_ops - 1; // host pads the list to an even length
@@ -405,8 +468,8 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
 #pragma unroll
       for (int i = 0; i < 2 * (HP + 1); ++i) __builtin_amdgcn_raw_buffer_store_b32(0u, none, 1024u * (unsigned)i, 0, 0); // (distinct offsets: identical stores would be merged)
     }
-    ExecRec  cur = XR(0);
-    IssueRec nx2 = IR((DIST < last) ? DIST : last); // the next operation whose loads go out
+    XRec cur = XR(0);
+    IRec nx2 = IR((DIST < last) ? DIST : last); // the next operation whose loads go out
 
     // One pipeline step: operation k; its loads are in (R, PC); Fprev = result of k-1, Fout = result of k-2
     // on entry and the result of k on exit.
@@ -414,7 +477,7 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
     auto step = [&](const int k, const int parity, Raw &R, u32x4 &PC, u32x4 &PC2, const u32x4 &PN, const u32x4 &PN2,
                     double (&Fout)[CS], unsigned &scout, const double (&Fprev)[CS], const unsigned scprev) {
       PHY_STAMP(k, 0)
-      ExecRec  nx1;
+      XRec     nx1;
       double2 *buf = reinterpret_cast<double2 *>(&lds_p[parity][0]);
       if constexpr (!early)
       { // the execute record of operation k+1 is the first thing the next step needs (its flags steer the operand
@@ -426,13 +489,16 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       { // Both records the previous step asked for (cur, nx2) are waited for HERE, before the first LDS read: scalar loads and
         // LDS share a counter and scalar loads return out of order, so one still in flight turns every counted wait for a
         // batch of matrix reads into a drain.  The matrices were staged by the previous step.
-        asm volatile("" ::"s"(uni(nx2.c1_scale.bytes)), "s"(uni(cur.dst_scale.bytes)));
+        if constexpr (compact) asm volatile("" ::"s"(uni(nx2.pmx)), "s"(uni(cur.dst_scale)));
+        else asm volatile("" ::"s"(uni(nx2.c1_scale.bytes)), "s"(uni(cur.dst_scale.bytes)));
         __builtin_amdgcn_sched_barrier(0);
       }
       __builtin_amdgcn_wave_barrier();
       const double *bufd = &lds_p[parity][0];
 
-      const unsigned fl = uni(cur.dst_data.x);
+      unsigned fl;
+      if constexpr (compact) fl = uni(cur.fl);
+      else fl = uni(cur.dst_data.x);
       double         u1[CS], u2[CS];
       unsigned       s1, s2;
       bool           one1, one2; // first-entry test of the all-ones shortcut
@@ -546,7 +612,7 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       }
 
       PHY_STAMP(k, 3)
-      IssueRec nx3;
+      IRec nx3;
       if constexpr (early)
       { // The last LDS result of the step has been consumed; from here to the stores the step issues no LDS read.  The scalar
         // records of the next step go out now and are first used at its head, a product, a rescaling and the stores later; and
@@ -591,15 +657,29 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       scout = sc;
       PHY_STAMP(k, 5)
       {
-        const __amdgpu_buffer_rsrc_t dr = rsrc(cur.dst_data), gr = rsrc(cur.dst_scale);
-#pragma unroll
-        for (int e = 0; e < HP; ++e)
+        // Compact records: a result that is not stored (most of a whole-tree list: kOpNoStore) issues no store at all -- a scalar
+        // branch on the record's flag around the five instructions and their descriptors.  Measured against the same stores through
+        // descriptors of size 0 (one scalar select each, the loop's counted waits unchanged): profiles/r13_nt_records.md.
+        __amdgpu_buffer_rsrc_t dr, gr;
+        bool                   st = true;
+        if constexpr (compact)
         {
-          u32x4 w;
-          __builtin_memcpy(&w, &Fout[2 * e], 16);
-          __builtin_amdgcn_raw_buffer_store_b128(w, dr, voff16, (unsigned)e * rowb, PHYHIP_STORE_AUX);
+          st = (fl & kRecStore) != 0;
+          dr = arena(q.partials, cur.dst_data, data_bytes);
+          gr = arena(q.scales, cur.dst_scale, scale_bytes);
         }
-        __builtin_amdgcn_raw_buffer_store_b32(sc, gr, voff4, 0, 0);
+        else { dr = rsrc(cur.dst_data); gr = rsrc(cur.dst_scale); }
+        if (st)
+        {
+#pragma unroll
+          for (int e = 0; e < HP; ++e)
+          {
+            u32x4 w;
+            __builtin_memcpy(&w, &Fout[2 * e], 16);
+            __builtin_amdgcn_raw_buffer_store_b128(w, dr, voff16, (unsigned)e * rowb, PHYHIP_STORE_AUX);
+          }
+          __builtin_amdgcn_raw_buffer_store_b32(sc, gr, voff4, 0, 0);
+        }
       }
       PHY_STAMP(k, 6)
       cur = nx1;

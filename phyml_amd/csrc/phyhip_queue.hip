@@ -382,6 +382,67 @@ static void fill_records(const Instance *I, const FlushPlan &f, IssueRec *ir, Ex
   }
 }
 
+// The list form of the lane-per-pattern nucleotide kernel reads compact records (NtIssue / NtExec, phyhip_kernels.hpp): the same
+// decisions as fill_records and child_descs -- which loads are live, which row the auxiliary dword comes from, what is forwarded,
+// the padded re-execution of an odd list's last operation -- said as flag bits and offsets from the three arenas.
+static bool compact_list_form(const Instance *I)
+{ // (the shapes launch_soa has an instantiation for; any other falls through to kernels that read descriptors)
+  if (!I->soa || I->perm) return false;
+  const int g = I->nt_groups;
+  return (I->C == 1 && g == 1) || (I->C == 2 && g <= 2) || (I->C == 3 && g == 1) || (I->C == 4 && (g == 1 || g == 2 || g == 4));
+}
+
+static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, NtExec *xr, int n_rec)
+{
+  const int    n_ops = f.n_ops;
+  const size_t data16 = buf_elems(I) * sizeof(double) / 16, scale16 = scale_elems(I) * 4 / 16, tip16 = (size_t)I->Ppad / 16; // (Ppad: a multiple of 64)
+  const size_t n_int = (size_t)(I->nbuf - I->tips);
+  if (n_int * data16 > 0xffffffffull || (size_t)I->tips * tip16 > 0xffffffffull || I->tips >= (1 << 24))
+    return fail(PHYHIP_ERROR_OUT_OF_RANGE, "an arena of this instance is beyond the reach of a record's offset (64 GiB, 2^24 tips)");
+  const unsigned matbytes = (unsigned)((size_t)I->C * I->S * I->S * sizeof(double));
+  auto at = [&](int k) -> const DevOp & { return I->pending[std::min(k, n_ops - 1)]; };
+  long long (&kinds)[2][5] = *reinterpret_cast<long long (*)[2][5]>(I->rec_stats + 2); // (phyhip_get_record_stats)
+  ++I->rec_stats[0];
+  for (int k = 0; k < n_rec; ++k)
+  {
+    const DevOp     &o  = at(k);
+    const int        e1 = k >= 1 ? at(k - 1).dest : -1;
+    const int        e2 = (k >= 2 && I->prefetch_dist == 2) ? at(k - 2).dest : -1;
+    const InlineDef *inl = (o.pad & (kOpInl1 | kOpInl2)) ? &I->pending_inl[std::min(k, n_ops - 1)] : nullptr;
+    NtIssue          r;
+    memset(&r, 0, sizeof r);
+    unsigned fl = 0;
+    auto child = [&](int c, int s, int pm, bool in_step) { // s: 0 child 1, 1 child 2 (the second bit of each pair of flags)
+      r.pm[s] = (unsigned)pm * matbytes;
+      if (in_step)
+      { // its first tip's row as the auxiliary dword, its second tip by index, its two matrices in the data slot and the spare word
+        r.fl |= (kRecIn1 | kRecA1 | kRecT1) << s | (unsigned)inl->b << 8;
+        r.data[s] = (unsigned)inl->pmA * matbytes; r.pmx = (unsigned)inl->pmB * matbytes;
+        r.aux[s] = (unsigned)((size_t)inl->a * tip16);
+        fl |= kOpCh1 << s;
+        ++kinds[s][1];
+        return;
+      }
+      const size_t b = (size_t)(c - I->tips);
+      if (c < I->tips) { r.fl |= (kRecA1 | kRecT1) << s; r.aux[s] = (unsigned)((size_t)c * tip16); fl |= kOpTip1 << s; ++kinds[s][0]; }
+      else if (c == e1) { fl |= s ? kOpF21 : kOpF11; ++kinds[s][2]; }
+      else if (c == e2) { fl |= s ? kOpF22 : kOpF12; ++kinds[s][3]; }
+      else
+      {
+        if (!I->no_loads) { r.fl |= (kRecL1 | kRecA1) << s; r.data[s] = (unsigned)(b * data16); r.aux[s] = (unsigned)(b * scale16); }
+        ++kinds[s][4];
+      }
+    };
+    child(o.c1, 0, o.pm1, inl && (o.pad & kOpInl1));
+    child(o.c2, 1, o.pm2, inl && (o.pad & kOpInl2));
+    ir[k] = r;
+    const size_t b = (size_t)(o.dest - I->tips);
+    xr[k].fl = fl | ((o.pad & kOpNoStore) ? 0u : kRecStore);
+    xr[k].dst_data = (unsigned)(b * data16); xr[k].dst_scale = (unsigned)(b * scale16); xr[k].pad = 0;
+  }
+  return 0;
+}
+
 // The queued operations as the kernel reads them: in a device slot (a list identical to one still sitting there -- repeated
 // Lk(NULL) on one topology -- is neither rebuilt nor re-uploaded), or, one or two operations of the pipelined kernels, in the
 // kernel arguments (phyhip_nt2.hpp): no staging, no copy command, and the device slots keep the long lists they cache
@@ -391,8 +452,11 @@ static int build_op_records(Instance *I, FlushPlan &f, TreeParams &q)
   const bool fat = f.fat;
   q.last_dest = -1;
   if (n_ops == 0) return 0;
-  const int    kind = fat ? I->prefetch_dist : 0, n_rec = n_ops + (n_ops & 1);
-  const size_t ib = sizeof(IssueRec) * n_rec, xb = sizeof(ExecRec) * n_rec;
+  // (a slot's kind: 0 DevOps, 1 / 2 descriptor records with loads that many operations ahead, 16 + that: compact records.  A
+  // command for the large-grid resident workgroups reads descriptors)
+  const bool   compact = fat && compact_list_form(I) && !f.big_cmd();
+  const int    kind = fat ? (compact ? 16 : 0) + I->prefetch_dist : 0, n_rec = n_ops + (n_ops & 1);
+  const size_t ib = (compact ? sizeof(NtIssue) : sizeof(IssueRec)) * n_rec, xb = (compact ? sizeof(NtExec) : sizeof(ExecRec)) * n_rec;
   int          hit = -1, rc = 0;
   for (int sl = 0; sl < I->ops_slots && hit < 0; ++sl)
     if (I->slot_kind[sl] == kind && I->slot_ops[sl].size() == (size_t)n_ops &&
@@ -415,10 +479,15 @@ static int build_op_records(Instance *I, FlushPlan &f, TreeParams &q)
       if ((rc = I->ring.alloc(bytes, I->stream, &st))) return rc;
     }
     if (!fat) memcpy(st, I->pending.data(), bytes);
+    else if (compact && !in_args)
+    {
+      if ((rc = fill_compact_records(I, f, reinterpret_cast<NtIssue *>(st), reinterpret_cast<NtExec *>((char *)st + ib), n_rec))) return rc;
+    }
     else fill_records(I, f, in_args ? q.arg_ir : reinterpret_cast<IssueRec *>(st), in_args ? q.arg_xr : reinterpret_cast<ExecRec *>((char *)st + ib), n_rec);
     if (in_args) { q.recs_in_args = 1; q.n_real_ops = n_ops; }
     else HIPCHK(hipMemcpyAsync(dst, st, bytes, hipMemcpyHostToDevice, I->stream)); // (reading short lists straight from the pinned staging memory instead was measured: no gain)
   }
+  if (hit >= 0 && compact) ++I->rec_stats[1];
   if (!fat) f.ro.ops = reinterpret_cast<const DevOp *>(dst);
   else if (!in_args) { f.d_irec = reinterpret_cast<const IssueRec *>(dst); f.d_xrec = reinterpret_cast<const ExecRec *>(dst + ib); }
   if (fat) q.last_dest = I->pending[n_ops - 1].dest;
