@@ -642,6 +642,17 @@ int phyhip_get_chained_stats(int instance, long long out[4]);
    its buffer -- padding records of odd lists included.  Sharded instances: the first shard's counters. */
 int phyhip_get_record_stats(int instance, long long out[12]);
 
+/* The step kinds of the compact lists built so far: out[8 * parity + kind], parity = the step's number in its list modulo 2
+   (the kernel's loop body holds an even and an odd step), padding records included.  Kind 0 is the generic step; 1 tip x
+   forwarded k-1, 2 forwarded k-1 x tip, 3 in-step x forwarded k-1, 4 forwarded k-1 x in-step, 5 in-step x tip, 6 tip x in-step,
+   7 unused.  A step gets a kind other than 0 only if every tip row it reads (an in-step child's two included) is one-hot
+   throughout.  Sharded instances: the first shard's counters. */
+int phyhip_get_step_kind_stats(int instance, long long out[16]);
+
+/* What the instance keeps per nucleotide tip row, computed from n state-set bytes: bit 0 every code is one-hot (1, 2, 4 or 8),
+   bit 1 some code is 15.  Host arithmetic only: needs no device. */
+int phyhip_tip_row_bits(const unsigned char *codes, long long n);
+
 /* ---- parsimony (src/pars.c) --------------------------------------------------------------------------------------------------- */
 
 /* Update_Partial_Pars (src/pars.c:239-393) and Pars / Pars_Core (src/pars.c:20-52, 397-437) on the device, in the reference's own

@@ -71,7 +71,7 @@ SYMBOLS = [
     "phyhip_calculate_eigen_lnl_dlnl", "phyhip_calculate_eigen_lnl", "phyhip_get_dot_prod", "phyhip_set_stream",
     "phyhip_synchronize", "phyhip_profile", "phyhip_profile_read", "phyhip_calculate_mixture_log_likelihood",
     "phyhip_calculate_mixture_eigen_lnl_dlnl", "phyhip_comm_get_unique_id", "phyhip_comm_init_rank", "phyhip_comm_size",
-    "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_get_deferred_stats", "phyhip_set_chained_buffers", "phyhip_get_chained_stats", "phyhip_get_record_stats", "phyhip_calculate_class_mixture_log_likelihood",
+    "phyhip_get_shard_range", "phyhip_profile_read_kernel", "phyhip_profile_read_collective", "phyhip_profile_read_traffic", "phyhip_profile_read_eigen", "phyhip_get_resident_stats", "phyhip_get_big_resident_stats", "phyhip_set_virtual_buffers", "phyhip_get_virtual_stats", "phyhip_get_deferred_stats", "phyhip_set_chained_buffers", "phyhip_get_chained_stats", "phyhip_get_record_stats", "phyhip_get_step_kind_stats", "phyhip_tip_row_bits", "phyhip_calculate_class_mixture_log_likelihood",
     "phyhip_calculate_class_mixture_eigen_lnl_dlnl", "phyhip_get_class_scale_factors", "phyhip_set_mixture_invariant_sites",
     "phyhip_calculate_edge_site_outputs_exact", "phyhip_calculate_node_state_posteriors", "phyhip_profile_read_node_posteriors",
     "phyhip_calculate_pairwise_ml_distances", "phyhip_set_pairwise_work_space", "phyhip_profile_read_pairwise",
@@ -185,6 +185,13 @@ def load():
         L.phyhip_get_last_error.restype = C.c_char_p
         _lib = L
     return _lib
+
+
+def tip_row_bits(codes):
+    """phyhip_tip_row_bits of a nucleotide tip row given as state-set bytes: bit 0 every code is one-hot, bit 1 some code is 15
+    (host arithmetic: needs no device)"""
+    a = np.ascontiguousarray(codes, dtype=np.uint8)
+    return int(load().phyhip_tip_row_bits(a.ctypes.data_as(C.c_void_p), C.c_longlong(a.size)))
 
 
 def _chk(rc):
@@ -735,6 +742,14 @@ class Instance:
         out = (C.c_longlong * 12)()
         _chk(self.L.phyhip_get_record_stats(self.id, out))
         return tuple(int(v) for v in out)
+
+    def step_kind_stats(self):
+        """phyhip_get_step_kind_stats: ((kinds 0-7 of the even steps), (of the odd steps)) over the compact lists built; kind 0 is
+        the generic step, 1 tip x forwarded k-1, 2 forwarded k-1 x tip, 3 in-step x forwarded k-1, 4 forwarded k-1 x in-step,
+        5 in-step x tip, 6 tip x in-step"""
+        out = (C.c_longlong * 16)()
+        _chk(self.L.phyhip_get_step_kind_stats(self.id, out))
+        return tuple(int(v) for v in out[:8]), tuple(int(v) for v in out[8:])
 
     def profile_read_eigen(self):
         """(ms, launches) of eigen_lr_kernel and of dlk_kernel since profile(1)"""

@@ -265,6 +265,12 @@ static int build_instance(Instance *I, const hipDeviceProp_t &prop)
   }
   HIPCHK(hipMalloc((void **)&I->d_tipcodes, (size_t)I->tips * I->Ppad));
   HIPCHK(hipMemset(I->d_tipcodes, 0, (size_t)I->tips * I->Ppad));
+  if (I->S == 4)
+  {
+    I->h_tiprows.assign((size_t)I->tips * I->P, 0);
+    I->tip_namb.assign((size_t)I->tips, I->P);
+    I->tip_n15.assign((size_t)I->tips, 0);
+  }
   if (I->perm)
   {
     HIPCHK(hipMalloc((void **)&I->d_tipmasks, (size_t)I->tips * I->Ppad * sizeof(uint32_t)));
@@ -456,6 +462,38 @@ int phyhip_finalize_instance(int instance)
 
 // ---- inputs --------------------------------------------------------------------------------------
 
+// What the instance keeps per nucleotide tip row (the byte is the state set): how many codes are not one-hot and how many are 15.
+// One predicate and one count for the exported restatement and for the setters of tip rows.
+static bool tip_code_ambiguous(unsigned m) { return !(m == 1u || m == 2u || m == 4u || m == 8u); }
+static void tip_row_counts(const unsigned char *codes, long long n, long long &namb, long long &n15)
+{
+  namb = n15 = 0;
+  for (long long p = 0; p < n; ++p)
+  {
+    namb += tip_code_ambiguous(codes[p]);
+    n15 += codes[p] == 15u;
+  }
+}
+static int tip_bits_of(long long namb, long long n15) { return (namb == 0 ? 1 : 0) | (n15 != 0 ? 2 : 0); }
+// The two bits of a row: 1 every code is one-hot, 2 some code is 15
+int phyhip_tip_row_bits(const unsigned char *codes, long long n)
+{
+  long long namb, n15;
+  tip_row_counts(codes, n, namb, n15);
+  return tip_bits_of(namb, n15);
+}
+
+// A row's bits as the counters say them; a change of either bit makes the compact lists in the device slots stale (their step
+// kinds were chosen under the old bits): they are rebuilt at their next launch
+static int tip_bits_now(const Instance *I, int tip) { return tip_bits_of(I->tip_namb[(size_t)tip], I->tip_n15[(size_t)tip]); }
+static void tip_bits_changed(Instance *I, int tip, int before)
+{
+  if (tip_bits_now(I, tip) == before) return;
+  for (int &k : I->slot_kind)
+    if (k >= 16) k = -1;
+}
+extern "C++" int phyhip_host::tip_row_bits(const Instance *I, int tip) { return I->h_tiprows.empty() ? 0 : tip_bits_now(I, tip); }
+
 static int set_tip_codes(Instance *I, int tip, const std::vector<uint8_t> &codes)
 {
   // what is queued runs on the old row -- and may leave tip x tip results virtual; those, and the ones that already are, are
@@ -465,6 +503,13 @@ static int set_tip_codes(Instance *I, int tip, const std::vector<uint8_t> &codes
   devirtualise_tip(I, tip);
   if ((rc = flush_sync(I))) return rc;
   HIPCHK(hipMemcpy(I->d_tipcodes + (size_t)tip * I->Ppad, codes.data(), (size_t)I->P, hipMemcpyHostToDevice));
+  if (!I->h_tiprows.empty())
+  {
+    const int before = tip_bits_now(I, tip);
+    memcpy(I->h_tiprows.data() + (size_t)tip * I->P, codes.data(), (size_t)I->P);
+    tip_row_counts(codes.data(), I->P, I->tip_namb[(size_t)tip], I->tip_n15[(size_t)tip]);
+    tip_bits_changed(I, tip, before);
+  }
   if (I->d_tipmasks)
   {
     std::vector<uint32_t> m((size_t)I->P);
@@ -553,6 +598,15 @@ int phyhip_set_tip_partials_at_pattern(int instance, int tipIndex, int pattern, 
   if ((rc = I->ring.alloc(16, I->stream, &st))) return rc;
   *reinterpret_cast<uint8_t *>(st) = (uint8_t)code;
   *(reinterpret_cast<uint32_t *>(st) + 1) = m;
+  if (!I->h_tiprows.empty())
+  {
+    const int before = tip_bits_now(I, tipIndex);
+    uint8_t  &was = I->h_tiprows[(size_t)tipIndex * I->P + pattern];
+    I->tip_namb[(size_t)tipIndex] += (long long)tip_code_ambiguous((unsigned)code) - (long long)tip_code_ambiguous(was);
+    I->tip_n15[(size_t)tipIndex] += (long long)(code == 15) - (long long)(was == 15);
+    was = (uint8_t)code;
+    tip_bits_changed(I, tipIndex, before);
+  }
   I->stream_dirty = true; I->touched_call = true;
   HIPCHK(hipMemcpyAsync(I->d_tipcodes + (size_t)tipIndex * I->Ppad + pattern, st, 1, hipMemcpyHostToDevice, I->stream));
   if (I->d_tipmasks)
@@ -1351,6 +1405,15 @@ int phyhip_get_record_stats(int instance, long long out[12])
   if (Group *G = get_group(instance)) return phyhip_get_record_stats(G->sub_id[0], out);
   GET_INST(I, instance);
   memcpy(out, I->rec_stats, sizeof I->rec_stats);
+  return PHYHIP_SUCCESS;
+}
+
+int phyhip_get_step_kind_stats(int instance, long long out[2 * 8])
+{
+  if (Group *G = get_group(instance)) return phyhip_get_step_kind_stats(G->sub_id[0], out);
+  GET_INST(I, instance);
+  static_assert(kNtStepKinds == 8, "out[2][8]");
+  memcpy(out, I->step_kinds, sizeof I->step_kinds);
   return PHYHIP_SUCCESS;
 }
 

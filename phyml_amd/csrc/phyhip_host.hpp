@@ -399,6 +399,13 @@ struct Instance
   size_t    ops_slot_bytes = 0;
   int       ops_cap = 0, ops_slots = 4, ops_slot = 0;
   long long rec_stats[12] = {0};  // phyhip_get_record_stats
+  long long step_kinds[2][kNtStepKinds] = {{0}}; // phyhip_get_step_kind_stats: [step parity][kind] over the compact lists built
+  // What the host knows about the tip rows (4 states: the byte is the state set): a mirror of the rows and, per row, how many
+  // of its P codes are not one-hot and how many are 15 -- fill_compact_records gives a step a straight-line kind only over rows
+  // that are one-hot throughout (tip_row_bits below).  A row never set holds zeros: no code of it is one-hot.
+  std::vector<uint8_t>   h_tiprows;            // [tips][P] (S == 4 only)
+  std::vector<long long> tip_namb, tip_n15;    // [tips]
+  std::vector<unsigned>  last_exec_fl;         // diag build: NtExec::fl of the last compact list built (printed beside the stamps of PHYHIP_ABLATE=8)
   int       grid = 0, grid_nt = 0, block_nt = 64;
 
   std::vector<DevOp>                     pending;
@@ -671,6 +678,7 @@ constexpr int kOpInl1 = 2, kOpInl2 = 4; // DevOp::pad bits 1, 2: child 1 / child
 void devirtualise(Instance *I, int buf);     // queue (in front) the storing operation that makes buffer `buf` real again, behind those of its unstored inputs
 void devirtualise_all(Instance *I);
 void devirtualise_matrix(Instance *I, int m);  // ... for every virtual buffer whose definition reads matrix m
+int  tip_row_bits(const Instance *I, int tip);  // phyhip.hip: 1 the row is one-hot throughout, 2 some code of it is 15 (0: not a 4-state instance)
 void devirtualise_tip(Instance *I, int tip);   // ... reads tip row `tip`
 void devirtualise_dependants(Instance *I, int buf); // ... for every deferred or chained buffer whose definition reads buffer `buf` (about to be written outside the queue)
 // snapshot slot w (0: the definition's first matrix, 1: its second) of internal buffer b in the matrix tables

@@ -132,6 +132,20 @@ enum : unsigned
   kRecIn1 = 64u, kRecIn2 = 128u, // child 1 / child 2 is computed in the step (kOpCh1 / kOpCh2)
   kRecStore = 256u            // NtExec::fl: the result is stored (else the step issues no store)
 };
+// NtExec::fl, bits 12-14: the step's kind (fill_compact_records).  0 is the generic step, which serves every operation; the others
+// name how the two children reach the step -- 1 tip x forwarded k-1, 2 forwarded k-1 x tip, 3 in-step x forwarded k-1, 4 forwarded
+// k-1 x in-step, 5 in-step x tip, 6 tip x in-step -- and promise that every tip row the step reads is one-hot throughout: the step
+// then runs a straight-line body without the tests that cannot fire (nt2_run, phyhip_nt2.hpp).  A kind is a hint: the generic
+// step computes the same bits.  PHYHIP_NT_KINDS: the kinds the host hands out (bit k: kind k), for measuring one at a time.
+constexpr unsigned kRecKindShift = 12u;
+constexpr int      kNtStepKinds  = 8;
+#ifndef PHYHIP_NT_KINDS
+#define PHYHIP_NT_KINDS 0x7e
+#endif
+// Which instantiations of traverse_nt2_kernel<C, G, ., 0, 2, INL> carry the bodies (traverse_nt2_mixed_kernel always does): two or
+// four lanes per pattern, except the two forms in which the bodies cost spilled scalar registers (<4, 2> without and <2, 2> with
+// in-step children).  Every other list form compiles the generic step alone, and the host hands its lists kind 0 throughout.
+constexpr bool nt2_bodied(int C, int G, bool INL) { return G >= 2 && !(C == 4 && G == 2 && !INL) && !(C == 2 && G == 2 && INL); }
 
 // Everything a traversal launch needs.  Passed by value (fits the 4 KiB kernarg segment easily).
 struct TreeParams

@@ -73,7 +73,7 @@ struct NtFresh
 // from its two tips and two matrices -- exactly the step the defining operation would have been (column look-ups or row sums,
 // the all-ones rule, the product, the rescaling rule) -- instead of that operation occupying a pipeline step of its own.  Costs
 // every step one more auxiliary dword and one more 16-byte matrix piece per lane; launched only for lists that have such children.
-template <int C, int G, bool DBG, int ARGS, int DIST = 2, int NW = 1, bool LREC = false, bool INL = false>
+template <int C, int G, bool DBG, int ARGS, int DIST = 2, int NW = 1, bool LREC = false, bool INL = false, bool BODIES = false>
 __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__restrict__ irec, const ExecRec *__restrict__ xrec,
                                         const double *pmats, // (not restrict: the prologue may rewrite entries)
                                         const uint8_t *__restrict__ tip_codes, unsigned long long *dbg, const NtFresh fr,
@@ -538,6 +538,121 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       const unsigned tcx = INL ? ((R.tx >> tsh) & 255u) : 0u;
       bool in1 = false, in2 = false;
       if constexpr (INL) { in1 = (fl & kOpCh1) != 0; in2 = (fl & kOpCh2) != 0; }
+      unsigned ones_mask = 0;    // bit c: category c is all ones in both children
+      bool     ones_any = false; // (wave-uniform) some lane passed the first-entry test: only then can ones_mask be set
+      // ---- the straight-line bodies (compact records: the step's kind, kRecKindShift in phyhip_kernels.hpp) ----
+      // The host names how the two children reach the step and promises that every tip row it reads is one-hot throughout.  A body
+      // is the generic step's arithmetic for that one combination -- the same products and sums on the same operands in the same
+      // order -- without what cannot take effect there: no chain of tests on the child kinds, no one-hot vote and no row-sum path
+      // for the tips, and no all-ones rule: a one-hot tip child is never all ones, and where both children could be (in-step x
+      // forwarded) the first-entry vote is taken on the forwarded result before anything else -- a wave in which it fires runs the
+      // generic step.  The LDS reads of both children are asked for before the first product.
+      // BODIES: the instantiations that carry them (nt2_bodied, phyhip_kernels.hpp) -- the one-lane shape, twice the entries per
+      // lane, has no registers for them; every other list form is the generic step as it was, and the host hands it kind 0 throughout.
+      constexpr bool bodied = BODIES && compact && G >= 2 && DIST == 2;
+      bool fast = false;
+      if constexpr (bodied)
+      {
+        auto col = [&](const double *Md, const unsigned m, double (&u)[CS]) { // one-hot tip: column s of its matrix (tip_u)
+          const int s = (m >> 1) - (m >> 3);
+#pragma unroll
+          for (int e = 0; e < CS; ++e) u[e] = Md[(c0 * S + e) * 4 + s];
+        };
+        auto rows = [&](const double2 *M, double2 (&m)[CL * 8]) {
+#pragma unroll
+          for (int i = 0; i < CL * 8; ++i) m[i] = M[c0 * 8 + i];
+        };
+        auto matvec_m = [&](const double2 (&m)[CL * 8], const double (&x)[CS], double (&u)[CS]) { // matvec_x on rows already read
+#pragma unroll
+          for (int c = 0; c < CL; ++c)
+#pragma unroll
+            for (int i = 0; i < S; ++i)
+            {
+              const double2 lo = m[c * 8 + 2 * i], hi = m[c * 8 + 2 * i + 1];
+              double        a  = lo.x * x[c * 4];
+              a = __builtin_fma(lo.y, x[c * 4 + 1], a);
+              a = __builtin_fma(hi.x, x[c * 4 + 2], a);
+              a = __builtin_fma(hi.y, x[c * 4 + 3], a);
+              u[c * 4 + i] = a;
+            }
+        };
+        // K1 / K2: 0 a one-hot tip, 1 the previous step's result, 2 an in-step child of two one-hot tips (at most one of the two)
+        auto body = [&](auto k1_, auto k2_) {
+          constexpr int K1 = decltype(k1_)::value, K2 = decltype(k2_)::value;
+          constexpr int PI = (K1 == 2) ? 0 : 1, PO = 1 - PI; // position of the in-step child (if any) and of the other one
+          constexpr int KO = (K1 == 2) ? K2 : (K2 == 2) ? K1 : -1;
+          if constexpr (K1 + K2 == 3)
+          {
+            if (__builtin_amdgcn_ballot_w64(Fprev[0] == 1.0) != 0) return;
+          }
+          fast = true;
+          if constexpr (K1 != 2 && K2 != 2)
+          { // tip x forwarded k-1, either way round
+            constexpr int PT = (K1 == 0) ? 0 : 1;
+            double2       mf[CL * 8];
+            double (&ut)[CS] = PT == 0 ? u1 : u2;
+            double (&uf)[CS] = PT == 0 ? u2 : u1;
+            col(bufd + PT * C * 16, PT == 0 ? tca : tcb, ut);
+            rows(buf + (1 - PT) * C * 8, mf);
+            matvec_m(mf, Fprev, uf);
+            (PT == 0 ? s1 : s2) = 0;
+            (PT == 0 ? s2 : s1) = scprev;
+          }
+          else if constexpr (INL)
+          { // in-step x (tip | forwarded k-1), either way round: the cherry of tip_u's column look-ups, its product and rescaling
+            // rule (cherry above, without the rule for two fully ambiguous tips), then its product with the step's matrix
+            double  ua[CS], ub[CS];
+            double2 mo[CL * 8], mi[CL * 8];
+            double (&ui)[CS] = PI == 0 ? u1 : u2;
+            double (&uo)[CS] = PI == 0 ? u2 : u1;
+            col(bufd + 2 * C * 16, PI == 0 ? tca : tcb, ua);
+            col(bufd + 3 * C * 16, tcx, ub);
+            if constexpr (KO == 0) col(bufd + PO * C * 16, PO == 0 ? tca : tcb, uo);
+            else rows(buf + PO * C * 8, mo);
+            unsigned mx = 0;
+#pragma unroll
+            for (int e = 0; e < CS; ++e)
+            {
+              XC[e] = ua[e] * ub[e];
+              mx    = max(mx, hi32(XC[e]));
+            }
+            if constexpr (KO == 1) matvec_m(mo, Fprev, uo);
+            if constexpr (G > 1)
+            {
+              if (!cls) mx = group_max(mx);
+            }
+            if (mx < kHiInvTwoToLarge && q.apply_scaling)
+            {
+#pragma unroll
+              for (int e = 0; e < CS; ++e) XC[e] *= kTwoToLarge;
+              scx = kLarge;
+            }
+            rows(buf + PI * C * 8, mi); // (behind the rescaling branch: with these 16 rows live across it the two-lane shape runs out of registers)
+            matvec_m(mi, XC, ui);
+            (PI == 0 ? s1 : s2) = scx;
+            (PI == 0 ? s2 : s1) = KO == 0 ? 0u : scprev;
+          }
+        };
+        using std::integral_constant;
+        constexpr unsigned on = PHYHIP_NT_KINDS;
+        switch ((fl >> kRecKindShift) & 7u)
+        {
+          case 1: if constexpr ((on >> 1) & 1) body(integral_constant<int, 0>(), integral_constant<int, 1>()); break;
+          case 2: if constexpr ((on >> 2) & 1) body(integral_constant<int, 1>(), integral_constant<int, 0>()); break;
+          case 3: if constexpr (INL && ((on >> 3) & 1)) body(integral_constant<int, 2>(), integral_constant<int, 1>()); break;
+          case 4: if constexpr (INL && ((on >> 4) & 1)) body(integral_constant<int, 1>(), integral_constant<int, 2>()); break;
+          case 5: if constexpr (INL && ((on >> 5) & 1)) body(integral_constant<int, 2>(), integral_constant<int, 0>()); break;
+          case 6: if constexpr (INL && ((on >> 6) & 1)) body(integral_constant<int, 0>(), integral_constant<int, 2>()); break;
+          default: break;
+        }
+      }
+      if (fast)
+      {
+        PHY_STAMP(k, 1)
+        PHY_STAMP(k, 2)
+      }
+      else
+      {
       // ---- child 1 ----
       if constexpr (INL)
       {
@@ -581,8 +696,8 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       PHY_STAMP(k, 2)
       // all-ones shortcut (src/avx.c:575-587): a category whose eight child entries are exactly 1.0 yields 1.0.
       // Only fully ambiguous subtrees get here; the full test runs when some lane passes the first-entry test.
-      unsigned ones_mask = 0; // bit c: category c is all ones in both children
-      if (__builtin_amdgcn_ballot_w64(one1 && one2))
+      ones_any = __builtin_amdgcn_ballot_w64(one1 && one2) != 0;
+      if (ones_any)
       {
         double ra[CS], rb[CS];
         unpack(R.a, ra);
@@ -611,6 +726,7 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
         }
       }
 
+      }
       PHY_STAMP(k, 3)
       IRec nx3;
       if constexpr (early)
@@ -635,12 +751,24 @@ __device__ __forceinline__ void nt2_run(const TreeParams &q, const IssueRec *__r
       PHY_STAMP(k, 4)
 
       unsigned mxh = 0;
+      if (bodied && !ones_any)
+      { // no lane of the wave passed the first-entry test (or the step's kind has no such test): ones_mask is 0 in every lane
 #pragma unroll
-      for (int e = 0; e < CS; ++e)
+        for (int e = 0; e < CS; ++e)
+        {
+          Fout[e] = u1[e] * u2[e];
+          mxh     = max(mxh, hi32(Fout[e]));
+        }
+      }
+      else
       {
-        const double v = ((ones_mask >> (e / 4)) & 1u) ? 1.0 : u1[e] * u2[e];
-        Fout[e] = v;
-        mxh     = max(mxh, hi32(v));
+#pragma unroll
+        for (int e = 0; e < CS; ++e)
+        {
+          const double v = ((ones_mask >> (e / 4)) & 1u) ? 1.0 : u1[e] * u2[e];
+          Fout[e] = v;
+          mxh     = max(mxh, hi32(v));
+        }
       }
       if constexpr (G > 1)
       { // the maximum runs over all categories of the pattern (src/avx.c:498-503): combine the category groups
@@ -882,7 +1010,7 @@ __global__ __launch_bounds__(64, DIST == 1 ? G + 1 : G) void traverse_nt2_kernel
   fr.up_idx = reinterpret_cast<const int *>(ka + offsetof(TreeParams, up_idx));
   fr.up_val = reinterpret_cast<const double *>(ka + offsetof(TreeParams, up_val));
   __shared__ __attribute__((aligned(16))) double lds_dot[(64 / G) * C * 4];
-  nt2_run<C, G, DBG, ARGS, DIST, 1, false, INL>(q, irec, xrec, pmats, tip_codes, dbg, fr, blockIdx.x, threadIdx.x, lds_dot);
+  nt2_run<C, G, DBG, ARGS, DIST, 1, false, INL, ARGS == 0 && DIST == 2 && nt2_bodied(C, G, INL)>(q, irec, xrec, pmats, tip_codes, dbg, fr, blockIdx.x, threadIdx.x, lds_dot);
 }
 
 // Whole-tree traversals of mid-sized alignments with TWO wave shapes in one launch (four categories).  The two-lanes-per-pattern
@@ -911,9 +1039,9 @@ __global__ __launch_bounds__(64, 2) void traverse_nt2_mixed_kernel(const TreePar
   fr.up_val = reinterpret_cast<const double *>(ka + offsetof(TreeParams, up_val));
   __shared__ __attribute__((aligned(16))) double lds_dot[32 * C * 4];
   if ((int)blockIdx.x < n2)
-    nt2_run<C, 2, false, 0, 2, 1, false, INL>(q, irec, xrec, pmats, tip_codes, nullptr, fr, blockIdx.x, threadIdx.x, lds_dot);
+    nt2_run<C, 2, false, 0, 2, 1, false, INL, true>(q, irec, xrec, pmats, tip_codes, nullptr, fr, blockIdx.x, threadIdx.x, lds_dot);
   else
-    nt2_run<C, 4, false, 0, 2, 1, false, INL>(q, irec, xrec, pmats, tip_codes, nullptr, fr, 2u * (unsigned)n2 + (blockIdx.x - (unsigned)n2),
+    nt2_run<C, 4, false, 0, 2, 1, false, INL, true>(q, irec, xrec, pmats, tip_codes, nullptr, fr, 2u * (unsigned)n2 + (blockIdx.x - (unsigned)n2),
                                               threadIdx.x, lds_dot, blockIdx.x);
 }
 

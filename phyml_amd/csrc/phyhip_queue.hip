@@ -402,6 +402,10 @@ static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, Nt
   const unsigned matbytes = (unsigned)((size_t)I->C * I->S * I->S * sizeof(double));
   auto at = [&](int k) -> const DevOp & { return I->pending[std::min(k, n_ops - 1)]; };
   long long (&kinds)[2][5] = *reinterpret_cast<long long (*)[2][5]>(I->rec_stats + 2); // (phyhip_get_record_stats)
+  // does the kernel this list is launched with carry the straight-line bodies (launch_nt2: the mixed kernels always, the others
+  // by nt2_bodied)?  A list of any other kernel is kind 0 throughout.
+  const bool mixed  = I->mix_n4 > 0 && I->C == 4 && I->nt_groups == 2 && !I->ablate;
+  const bool bodied = I->prefetch_dist == 2 && I->nt_groups >= 2 && (mixed || nt2_bodied(I->C, I->nt_groups, f.has_inl));
   ++I->rec_stats[0];
   for (int k = 0; k < n_rec; ++k)
   {
@@ -412,10 +416,13 @@ static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, Nt
     NtIssue          r;
     memset(&r, 0, sizeof r);
     unsigned fl = 0;
+    int      how[2] = {-1, -1}; // for the step's kind: 0 a tip, 1 forwarded k-1, 2 in-step -- over one-hot rows only; -1 anything else
+    auto     onehot = [&](int tip) { return (tip_row_bits(I, tip) & 1) != 0; };
     auto child = [&](int c, int s, int pm, bool in_step) { // s: 0 child 1, 1 child 2 (the second bit of each pair of flags)
       r.pm[s] = (unsigned)pm * matbytes;
       if (in_step)
       { // its first tip's row as the auxiliary dword, its second tip by index, its two matrices in the data slot and the spare word
+        if (onehot(inl->a) && onehot(inl->b)) how[s] = 2;
         r.fl |= (kRecIn1 | kRecA1 | kRecT1) << s | (unsigned)inl->b << 8;
         r.data[s] = (unsigned)inl->pmA * matbytes; r.pmx = (unsigned)inl->pmB * matbytes;
         r.aux[s] = (unsigned)((size_t)inl->a * tip16);
@@ -424,8 +431,8 @@ static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, Nt
         return;
       }
       const size_t b = (size_t)(c - I->tips);
-      if (c < I->tips) { r.fl |= (kRecA1 | kRecT1) << s; r.aux[s] = (unsigned)((size_t)c * tip16); fl |= kOpTip1 << s; ++kinds[s][0]; }
-      else if (c == e1) { fl |= s ? kOpF21 : kOpF11; ++kinds[s][2]; }
+      if (c < I->tips) { r.fl |= (kRecA1 | kRecT1) << s; r.aux[s] = (unsigned)((size_t)c * tip16); fl |= kOpTip1 << s; ++kinds[s][0]; if (onehot(c)) how[s] = 0; }
+      else if (c == e1) { fl |= s ? kOpF21 : kOpF11; ++kinds[s][2]; how[s] = 1; }
       else if (c == e2) { fl |= s ? kOpF22 : kOpF12; ++kinds[s][3]; }
       else
       {
@@ -436,9 +443,16 @@ static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, Nt
     child(o.c1, 0, o.pm1, inl && (o.pad & kOpInl1));
     child(o.c2, 1, o.pm2, inl && (o.pad & kOpInl2));
     ir[k] = r;
+    // the step's kind (kRecKindShift, phyhip_kernels.hpp): [child 1][child 2] -> kind; 0 = the generic step
+    static const unsigned char kind_of[3][3] = {{0, 1, 6}, {2, 0, 4}, {5, 3, 0}};
+    unsigned kind = (how[0] >= 0 && how[1] >= 0) ? kind_of[how[0]][how[1]] : 0u;
+    if (!((PHYHIP_NT_KINDS >> kind) & 1) || !bodied) kind = 0;
+    ++I->step_kinds[k & 1][kind];
+    fl |= kind << kRecKindShift;
     const size_t b = (size_t)(o.dest - I->tips);
     xr[k].fl = fl | ((o.pad & kOpNoStore) ? 0u : kRecStore);
     xr[k].dst_data = (unsigned)(b * data16); xr[k].dst_scale = (unsigned)(b * scale16); xr[k].pad = 0;
+    if (kDiag) { I->last_exec_fl.resize((size_t)n_rec); I->last_exec_fl[(size_t)k] = xr[k].fl; }
   }
   return 0;
 }
@@ -838,8 +852,8 @@ template <typename K> static void launch_aa_form(K kernel, Instance *I, dim3 blk
 
 #ifdef PHYHIP_DIAG
 // PHYHIP_ABLATE=8: the cycle stamps one wave left (the sixth launch's; costs a sync), printed to stderr
-static int print_stamps(Instance *I, int n_steps, bool load_issue, int &printed)
-{
+static int print_stamps(Instance *I, int n_steps, bool load_issue, int &printed, const std::vector<unsigned> *fl = nullptr)
+{ // fl: the execute flags of a compact list (NtExec::fl): the step's kind and how its children reach it are printed beside its stamps
   if (printed++ != 5) return 0;
   unsigned long long h[64 * 8];
   HIPCHK(hipMemcpyAsync(h, I->d_dbg, sizeof h, hipMemcpyDeviceToHost, I->stream));
@@ -850,6 +864,12 @@ static int print_stamps(Instance *I, int n_steps, bool load_issue, int &printed)
     for (int i = 1; i < 7; ++i) fprintf(stderr, " %6lld", (long long)(h[k * 8 + i] - h[k * 8 + i - 1]));
     if (k + 1 < 64) fprintf(stderr, "  | next %6lld", (long long)(h[(k + 1) * 8] - h[k * 8 + 6]));
     if (load_issue) fprintf(stderr, "  | load issue %6lld of segment 4", (long long)(h[k * 8 + 7] - h[k * 8 + 3]));
+    if (fl && k < (int)fl->size())
+    {
+      const unsigned x = (*fl)[(size_t)k];
+      auto           how = [&](int s) { return (x & (kOpCh1 << s)) ? "in-step" : (x & (kOpTip1 << s)) ? "tip" : (x & (s ? kOpF21 : kOpF11)) ? "fwd1" : (x & (s ? kOpF22 : kOpF12)) ? "fwd2" : "loaded"; };
+      fprintf(stderr, "  | kind %u: %s x %s%s", (x >> kRecKindShift) & 7u, how(0), how(1), (x & kRecStore) ? ", stored" : "");
+    }
     fprintf(stderr, "\n");
   }
   return 0;
@@ -860,10 +880,13 @@ static int launch_nt2_diag(Instance *I, const FlushPlan &f, const TreeParams &q)
 {
   if (!((I->ablate & 8) && I->C == 4 && I->nt_groups <= 2)) return kNotLaunched;
   if (!I->d_dbg) HIPCHK(hipMalloc((void **)&I->d_dbg, 64 * 8 * 8));
-  if (I->nt_groups == 2) launch_nt2_form(traverse_nt2_kernel<4, 2, true>, I, f, q, I->d_dbg);
+  // (a list with in-step children -- the mostly-unstored list a default traversal runs -- needs the instantiation that stages four matrices)
+  if (I->nt_groups == 2 && f.has_inl) launch_nt2_form(traverse_nt2_kernel<4, 2, true, 0, 2, true>, I, f, q, I->d_dbg);
+  else if (f.has_inl) return fail(PHYHIP_ERROR_NO_IMPLEMENTATION, "PHYHIP_ABLATE=8: the stamped form with in-step children is the two-lane one");
+  else if (I->nt_groups == 2) launch_nt2_form(traverse_nt2_kernel<4, 2, true>, I, f, q, I->d_dbg);
   else launch_nt2_form(traverse_nt2_kernel<4, 1, true>, I, f, q, I->d_dbg);
   static int printed = 0;
-  return print_stamps(I, q.n_ops, true, printed);
+  return print_stamps(I, q.n_ops, true, printed, &I->last_exec_fl);
 }
 
 static int launch_aa_diag(Instance *I, dim3 blk, const FlushPlan &f, const TreeParams &q)
@@ -1032,7 +1055,7 @@ static int flush_impl(Instance *I, const EdgeEval *ee)
   // virtual buffers: what the queue reads of them is (re)computed in front of its reader; a long list of the two pipelined
   // kernels with two-deep register forwarding leaves its own tip x tip results virtual (rewrite_pending)
   rewrite_pending(I, ee, (I->soa || I->perm) && !I->generic_nt && I->prefetch_dist == 2 && !I->class_axis && !I->generic_loop &&
-                             !I->ablate && !I->no_loads);
+                             !(I->ablate & ~8) && !I->no_loads); // (PHYHIP_ABLATE=8 stamps the list a default traversal runs)
   I->unstored.keep_clear();
   const int n_ops = f.n_ops = (int)I->pending.size();
   int       rc = 0;
