@@ -29,6 +29,9 @@
 //   phyhip_matrix_queue.hpp  the table of queued matrix refreshes (Instance::rebuilds, Instance::uploads: enqueue with the last
 //                        writer winning, snapshot slots, clear).  Plain host C++, no HIP; the command that took such a queue
 //                        along: SentCommand below
+//   phyhip_step_plan.hpp  how each child of each step of a launch reaches it (tip, forwarded in registers, in-step, loaded) and
+//                        whether the step stores: the one statement of the register window, read by the record encoders, the
+//                        traffic count and the planner of unstored buffers.  Plain host C++, no HIP
 // The device side: phyhip_kernels.hpp (first-generation, eigen-basis, mixture and matrix kernels), phyhip_nt2.hpp, phyhip_aa.hpp,
 // phyhip_big.hpp, and what they share --
 //   phyhip_tail.hpp      Lk_Core's per-pattern tail: invariant_lk (every kernel that has the loop), the +I mix, the SMALL floor
@@ -43,6 +46,7 @@
 #include "phyhip_nt2.hpp"
 #include "phyhip_big.hpp"
 #include "phyhip_matrix_queue.hpp"
+#include "phyhip_step_plan.hpp"
 
 #include <rccl/rccl.h>
 
@@ -405,6 +409,7 @@ struct Instance
   // that are one-hot throughout (tip_row_bits below).  A row never set holds zeros: no code of it is one-hot.
   std::vector<uint8_t>   h_tiprows;            // [tips][P] (S == 4 only)
   std::vector<long long> tip_namb, tip_n15;    // [tips]
+  std::vector<StepPlan>  step_plan;            // the plan of the list being launched (phyhip_step_plan.hpp; a short launch keeps its two entries in its FlushPlan)
   std::vector<unsigned>  last_exec_fl;         // diag build: NtExec::fl of the last compact list built (printed beside the stamps of PHYHIP_ABLATE=8)
   int       grid = 0, grid_nt = 0, block_nt = 64;
 
@@ -683,7 +688,12 @@ void devirtualise_tip(Instance *I, int tip);   // ... reads tip row `tip`
 void devirtualise_dependants(Instance *I, int buf); // ... for every deferred or chained buffer whose definition reads buffer `buf` (about to be written outside the queue)
 // snapshot slot w (0: the definition's first matrix, 1: its second) of internal buffer b in the matrix tables
 inline int shadow_slot(const Instance *I, int b, int w) { return I->nmat + 2 * (b - I->tips) + w; }
-void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise);
+constexpr PadBits kPadBits{kOpNoStore, {kOpInl1, kOpInl2}}; // (for phyhip_step_plan.hpp)
+// forwarding: the register window of the kernel a LIST of this queue would run with, where such a list may leave results unstored
+// (depth 0: everything the queue computes is stored)
+void rewrite_pending(Instance *I, const EdgeEval *ee, RegWindow forwarding);
+// ... said by a caller with no kernel in mind (phyhip_update_eigen_lr: false; the model drivers under tests/): two-deep forwarding or none
+inline void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise) { rewrite_pending(I, ee, RegWindow{may_virtualise ? 2 : 0}); }
 
 // ---- resident evaluators: host side -----------------------------------------------------------------------------
 constexpr int kResidentMaxGrid = 64;   // resident evaluator: alignments of up to this many dLk workgroups

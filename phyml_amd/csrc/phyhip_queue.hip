@@ -140,14 +140,21 @@ struct FlushPlan
   bool big_fit = false, big_try = false, big_take = false; // the large-grid ones may serve it; the stream lets them; they are there
   bool one_shot = false; // ... or they are not, and their kernel is launched for this one evaluation (BigArgs::n_one_shot)
   bool big_cmd() const { return big_take || one_shot; } // (records for that kernel: no forwarding between two operations)
-  // the operation records (build_op_records)
+  // the operation records (place_op_records, build_op_records)
   bool             fat = false, has_inl = false; // record pairs of the pipelined kernels, not DevOps; some operation computes a virtual child in its own step
+  RegWindow        window{0};                    // how far back the launch's kernel forwards results in registers (reg_window)
+  StepPlan         plan_short[2];                // the step plan of a launch of one or two records; a longer one: Instance::step_plan
+  const StepPlan  *plan = nullptr;               // ... once somebody asked for it (step_plan)
+  bool             compact = false;              // compact records (NtIssue / NtExec), not descriptors
+  int              slot_hit = -1;                // the device slot that still holds this very list, or -1
+  bool             in_args = false;              // one or two operations of the pipelined kernels, in the kernel arguments
   std::vector<int> aa_slot, aa_need;             // the 20-state LDS ring, per item (plan_aa_ring)
   const IssueRec  *d_irec = nullptr;             // ... in a device slot (nullptr: in the kernel arguments)
   const ExecRec   *d_xrec = nullptr;
   RO               ro;                           // ... or slim DevOps (RO::ops), and the tables every kernel reads
   // the launch
   bool mixed = false;     // a list-form launch of an instance with two wave shapes: traverse_nt2_mixed_kernel's grid, one record per workgroup
+  bool bodied = false;    // ... or of any kernel that carries the straight-line step bodies: its compact records name step kinds
   int  soa_grid = 0;      // workgroups of the lane-per-pattern kernel in this launch
   int  host_sum_n = 0;    // > 0: the host adds this many posted records (Instance::host_sum_n)
   bool fused_sum = false; // the traversal kernel's last workgroup finishes the sum
@@ -308,15 +315,18 @@ static void plan_aa_ring(const Instance *I, const EdgeEval *ee, FlushPlan &f, Tr
   if (ee) { q.aa_e_slot = f.aa_slot[n_rec]; q.aa_e_need = f.aa_need[n_rec]; }
 }
 
+// The register window of the kernel that runs the records (phyhip_step_plan.hpp): the one place that chooses its depth
+static RegWindow reg_window(const Instance *I, bool fat, bool big_cmd) { return RegWindow{(!fat || big_cmd) ? 0 : (I->prefetch_dist == 2 ? 2 : 1)}; }
+
 static Desc make_desc(const void *base, size_t bytes, unsigned x) { return Desc{(unsigned long long)(uintptr_t)base, (unsigned)bytes, x}; }
 
 // One child of an operation into the three descriptors the issue stage reads; returns the operation's flag bits it sets.
-// e1 / e2: the results still in registers (the previous two operations'); in_step: the child is a virtual tip x tip result
-// computed inside this operation's step, and this is how
-static unsigned child_descs(const Instance *I, int c, bool second, int e1, int e2, unsigned pmoff, unsigned matbytes, const InlineDef *in_step,
+// reach: how the child comes to the step (the launch's step plan, phyhip_step_plan.hpp); in_step: the definition of the operation's
+// in-step child -- a virtual tip x tip result computed inside its step, and this is how
+static unsigned child_descs(const Instance *I, int c, bool second, Reach reach, unsigned pmoff, unsigned matbytes, const InlineDef *in_step,
                             Desc &data, Desc &scale, Desc &tip)
 {
-  if (in_step)
+  if (reach == Reach::InStep)
   { // (kOpCh1 / kOpCh2, phyhip_kernels.hpp) no load of its own -- its two matrices' offsets, its first tip's row in the auxiliary
     // slot, its second tip's row in the tip slot
     const unsigned long long ab = (unsigned long long)((unsigned)in_step->pmA * matbytes) | ((unsigned long long)((unsigned)in_step->pmB * matbytes) << 32);
@@ -333,9 +343,8 @@ static unsigned child_descs(const Instance *I, int c, bool second, int e1, int e
     }
     return second ? kOpCh2 : kOpCh1;
   }
-  const bool   t = c < I->tips;
-  const bool   f1 = !t && c == e1, f2 = !t && !f1 && c == e2;
-  const bool   ld = !t && !f1 && !f2 && !I->no_loads;
+  const bool   t = reach == Reach::Tip, f1 = reach == Reach::Prev1, f2 = reach == Reach::Prev2;
+  const bool   ld = reach == Reach::Loaded && !I->no_loads; // (PHYHIP_NOLOADS zeroes the load; the child's reach stays what it is)
   const size_t b = ld ? (size_t)(c - I->tips) : 0;
   data  = make_desc(I->d_partials + b * buf_elems(I), ld ? buf_elems(I) * sizeof(double) : 0, pmoff);
   scale = make_desc(I->d_scales + b * scale_elems(I), ld ? scale_elems(I) * 4 : 0, 0);
@@ -350,32 +359,29 @@ static unsigned child_descs(const Instance *I, int c, bool second, int e1, int e
 
 // One record pair per operation, all address arithmetic done here once.  The kernel alternates two register sets, so an odd
 // list is padded with a re-execution of its last operation (idempotent: same inputs, same output, same address) whose
-// forwarding flags are computed for its own position.
-static void fill_records(const Instance *I, const FlushPlan &f, IssueRec *ir, ExecRec *xr, int n_rec)
+// forwarding flags are those of its own position (the step plan says both).
+static void fill_records(const Instance *I, const FlushPlan &f, const StepPlan *plan, IssueRec *ir, ExecRec *xr, int n_rec)
 {
-  const int      n_ops = f.n_ops;
   const size_t   bufbytes = buf_elems(I) * sizeof(double);
   // spare word of the data descriptors: byte offset of the child's matrix (natural table, or the MFMA A-fragment table, 20 states)
   const unsigned matbytes = I->perm ? (unsigned)(kAaMat * sizeof(double)) : (unsigned)((size_t)I->C * I->S * I->S * sizeof(double));
-  auto at = [&](int k) -> const DevOp & { return I->pending[std::min(k, n_ops - 1)]; };
   for (int k = 0; k < n_rec; ++k)
   {
-    const DevOp     &o  = at(k);
-    const int        e1 = (k >= 1 && !f.big_cmd()) ? at(k - 1).dest : -1;
-    const int        e2 = (k >= 2 && I->prefetch_dist == 2) ? at(k - 2).dest : -1;
-    const InlineDef *inl = (o.pad & (kOpInl1 | kOpInl2)) ? &I->pending_inl[std::min(k, n_ops - 1)] : nullptr;
+    const StepPlan  &p = plan[k];
+    const DevOp     &o = I->pending[p.op];
+    const InlineDef *inl = (p.reach[0] == Reach::InStep || p.reach[1] == Reach::InStep) ? &I->pending_inl[p.op] : nullptr;
     unsigned         fl = 0;
-    fl |= child_descs(I, o.c1, false, e1, e2, (unsigned)o.pm1 * matbytes, matbytes, (o.pad & kOpInl1) ? inl : nullptr, ir[k].c1_data, ir[k].c1_scale, ir[k].c1_tip);
-    fl |= child_descs(I, o.c2, true, e1, e2, (unsigned)o.pm2 * matbytes, matbytes, (o.pad & kOpInl2) ? inl : nullptr, ir[k].c2_data, ir[k].c2_scale, ir[k].c2_tip);
+    fl |= child_descs(I, o.c1, false, p.reach[0], (unsigned)o.pm1 * matbytes, matbytes, inl, ir[k].c1_data, ir[k].c1_scale, ir[k].c1_tip);
+    fl |= child_descs(I, o.c2, true, p.reach[1], (unsigned)o.pm2 * matbytes, matbytes, inl, ir[k].c2_data, ir[k].c2_scale, ir[k].c2_tip);
     const size_t b = (size_t)(o.dest - I->tips);
-    const bool   st_on = !(o.pad & kOpNoStore); // (a result that stays virtual: stores through descriptors of size 0 are dropped)
+    const bool   st_on = p.stored; // (a result that stays virtual: stores through descriptors of size 0 are dropped)
     xr[k].dst_data  = make_desc(I->d_partials + b * buf_elems(I), st_on ? bufbytes : 0, fl);
     xr[k].dst_scale = make_desc(I->d_scales + b * scale_elems(I), st_on ? scale_elems(I) * 4 : 0, 0);
     if (I->perm && f.has_inl)
     { // the ring item of this operation: first table slot (consumers: dst_scale.x; loader: c2_tip.x), what must be released
       // before it is written (c1_tip.bytes), and -- with an in-step child -- its two tables' offsets and its second tip's masks
       const unsigned long long ab = inl ? ((unsigned long long)((unsigned)inl->pmA * matbytes) | ((unsigned long long)((unsigned)inl->pmB * matbytes) << 32)) : 0ull;
-      ir[k].c1_tip = make_desc(reinterpret_cast<const void *>((uintptr_t)ab), (size_t)f.aa_need[k], inl ? ((o.pad & kOpInl1) ? 1u : 2u) : 0u);
+      ir[k].c1_tip = make_desc(reinterpret_cast<const void *>((uintptr_t)ab), (size_t)f.aa_need[k], inl ? (p.reach[0] == Reach::InStep ? 1u : 2u) : 0u);
       ir[k].c2_tip = make_desc(I->d_tipmasks + (size_t)(inl ? inl->b : 0) * I->Ppad, inl ? (size_t)I->Ppad * 4 : 0, (unsigned)f.aa_slot[k]);
       xr[k].dst_scale.x = (unsigned)f.aa_slot[k];
     }
@@ -392,69 +398,110 @@ static bool compact_list_form(const Instance *I)
   return (I->C == 1 && g == 1) || (I->C == 2 && g <= 2) || (I->C == 3 && g == 1) || (I->C == 4 && (g == 1 || g == 2 || g == 4));
 }
 
-static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, NtExec *xr, int n_rec)
+static int fill_compact_records(Instance *I, const FlushPlan &f, const StepPlan *plan, NtIssue *ir, NtExec *xr, int n_rec)
 {
-  const int    n_ops = f.n_ops;
   const size_t data16 = buf_elems(I) * sizeof(double) / 16, scale16 = scale_elems(I) * 4 / 16, tip16 = (size_t)I->Ppad / 16; // (Ppad: a multiple of 64)
   const size_t n_int = (size_t)(I->nbuf - I->tips);
   if (n_int * data16 > 0xffffffffull || (size_t)I->tips * tip16 > 0xffffffffull || I->tips >= (1 << 24))
     return fail(PHYHIP_ERROR_OUT_OF_RANGE, "an arena of this instance is beyond the reach of a record's offset (64 GiB, 2^24 tips)");
   const unsigned matbytes = (unsigned)((size_t)I->C * I->S * I->S * sizeof(double));
-  auto at = [&](int k) -> const DevOp & { return I->pending[std::min(k, n_ops - 1)]; };
-  long long (&kinds)[2][5] = *reinterpret_cast<long long (*)[2][5]>(I->rec_stats + 2); // (phyhip_get_record_stats)
-  // does the kernel this list is launched with carry the straight-line bodies (launch_nt2: the mixed kernels always, the others
-  // by nt2_bodied)?  A list of any other kernel is kind 0 throughout.
-  const bool mixed  = I->mix_n4 > 0 && I->C == 4 && I->nt_groups == 2 && !I->ablate;
-  const bool bodied = I->prefetch_dist == 2 && I->nt_groups >= 2 && (mixed || nt2_bodied(I->C, I->nt_groups, f.has_inl));
+  long long (&kinds)[2][5] = *reinterpret_cast<long long (*)[2][5]>(I->rec_stats + 2); // (phyhip_get_record_stats: per child, by reach)
+  static const int stat_of[5] = {0, 2, 3, 1, 4}; // Reach -> its column there: tip, in-step, forwarded one / two steps, loaded
+  auto onehot = [&](int tip) { return (tip_row_bits(I, tip) & 1) != 0; };
   ++I->rec_stats[0];
   for (int k = 0; k < n_rec; ++k)
   {
-    const DevOp     &o  = at(k);
-    const int        e1 = k >= 1 ? at(k - 1).dest : -1;
-    const int        e2 = (k >= 2 && I->prefetch_dist == 2) ? at(k - 2).dest : -1;
-    const InlineDef *inl = (o.pad & (kOpInl1 | kOpInl2)) ? &I->pending_inl[std::min(k, n_ops - 1)] : nullptr;
+    const StepPlan  &p = plan[k];
+    const DevOp     &o = I->pending[p.op];
+    const InlineDef *inl = (p.reach[0] == Reach::InStep || p.reach[1] == Reach::InStep) ? &I->pending_inl[p.op] : nullptr;
     NtIssue          r;
     memset(&r, 0, sizeof r);
     unsigned fl = 0;
-    int      how[2] = {-1, -1}; // for the step's kind: 0 a tip, 1 forwarded k-1, 2 in-step -- over one-hot rows only; -1 anything else
-    auto     onehot = [&](int tip) { return (tip_row_bits(I, tip) & 1) != 0; };
-    auto child = [&](int c, int s, int pm, bool in_step) { // s: 0 child 1, 1 child 2 (the second bit of each pair of flags)
-      r.pm[s] = (unsigned)pm * matbytes;
-      if (in_step)
-      { // its first tip's row as the auxiliary dword, its second tip by index, its two matrices in the data slot and the spare word
-        if (onehot(inl->a) && onehot(inl->b)) how[s] = 2;
-        r.fl |= (kRecIn1 | kRecA1 | kRecT1) << s | (unsigned)inl->b << 8;
-        r.data[s] = (unsigned)inl->pmA * matbytes; r.pmx = (unsigned)inl->pmB * matbytes;
-        r.aux[s] = (unsigned)((size_t)inl->a * tip16);
-        fl |= kOpCh1 << s;
-        ++kinds[s][1];
-        return;
-      }
+    bool     rows_onehot[2] = {false, false}; // for the step's kind: every tip row the child reads is one-hot throughout
+    for (int s = 0; s < 2; ++s) // s: 0 child 1, 1 child 2 (the second bit of each pair of flags)
+    {
+      const int    c = s ? o.c2 : o.c1;
       const size_t b = (size_t)(c - I->tips);
-      if (c < I->tips) { r.fl |= (kRecA1 | kRecT1) << s; r.aux[s] = (unsigned)((size_t)c * tip16); fl |= kOpTip1 << s; ++kinds[s][0]; if (onehot(c)) how[s] = 0; }
-      else if (c == e1) { fl |= s ? kOpF21 : kOpF11; ++kinds[s][2]; how[s] = 1; }
-      else if (c == e2) { fl |= s ? kOpF22 : kOpF12; ++kinds[s][3]; }
-      else
+      r.pm[s] = (unsigned)(s ? o.pm2 : o.pm1) * matbytes;
+      ++kinds[s][stat_of[(int)p.reach[s]]];
+      switch (p.reach[s])
       {
-        if (!I->no_loads) { r.fl |= (kRecL1 | kRecA1) << s; r.data[s] = (unsigned)(b * data16); r.aux[s] = (unsigned)(b * scale16); }
-        ++kinds[s][4];
+        case Reach::InStep: // its first tip's row as the auxiliary dword, its second tip by index, its two matrices in the data slot and the spare word
+          rows_onehot[s] = onehot(inl->a) && onehot(inl->b);
+          r.fl |= (kRecIn1 | kRecA1 | kRecT1) << s | (unsigned)inl->b << 8;
+          r.data[s] = (unsigned)inl->pmA * matbytes; r.pmx = (unsigned)inl->pmB * matbytes;
+          r.aux[s] = (unsigned)((size_t)inl->a * tip16);
+          fl |= kOpCh1 << s;
+          break;
+        case Reach::Tip:
+          rows_onehot[s] = onehot(c);
+          r.fl |= (kRecA1 | kRecT1) << s; r.aux[s] = (unsigned)((size_t)c * tip16);
+          fl |= kOpTip1 << s;
+          break;
+        case Reach::Prev1: fl |= s ? kOpF21 : kOpF11; break;
+        case Reach::Prev2: fl |= s ? kOpF22 : kOpF12; break;
+        case Reach::Loaded: // (PHYHIP_NOLOADS zeroes the load; the child's reach stays what it is)
+          if (!I->no_loads) { r.fl |= (kRecL1 | kRecA1) << s; r.data[s] = (unsigned)(b * data16); r.aux[s] = (unsigned)(b * scale16); }
+          break;
       }
-    };
-    child(o.c1, 0, o.pm1, inl && (o.pad & kOpInl1));
-    child(o.c2, 1, o.pm2, inl && (o.pad & kOpInl2));
+    }
     ir[k] = r;
-    // the step's kind (kRecKindShift, phyhip_kernels.hpp): [child 1][child 2] -> kind; 0 = the generic step
-    static const unsigned char kind_of[3][3] = {{0, 1, 6}, {2, 0, 4}, {5, 3, 0}};
-    unsigned kind = (how[0] >= 0 && how[1] >= 0) ? kind_of[how[0]][how[1]] : 0u;
-    if (!((PHYHIP_NT_KINDS >> kind) & 1) || !bodied) kind = 0;
+    // the step's kind, where the kernel this list is launched with carries the straight-line bodies (FlushPlan::bodied); a list
+    // of any other kernel is kind 0 throughout
+    unsigned kind = kind_of(p, rows_onehot);
+    if (!((PHYHIP_NT_KINDS >> kind) & 1) || !f.bodied) kind = 0;
     ++I->step_kinds[k & 1][kind];
     fl |= kind << kRecKindShift;
     const size_t b = (size_t)(o.dest - I->tips);
-    xr[k].fl = fl | ((o.pad & kOpNoStore) ? 0u : kRecStore);
+    xr[k].fl = fl | (p.stored ? kRecStore : 0u);
     xr[k].dst_data = (unsigned)(b * data16); xr[k].dst_scale = (unsigned)(b * scale16); xr[k].pad = 0;
     if (kDiag) { I->last_exec_fl.resize((size_t)n_rec); I->last_exec_fl[(size_t)k] = xr[k].fl; }
   }
   return 0;
+}
+
+// (a slot's kind: 0 DevOps, 1 / 2 descriptor records with loads that many operations ahead, 16 + that: compact records.  A
+// command for the large-grid resident workgroups reads descriptors)
+static int slot_kind_of(const Instance *I, const FlushPlan &f) { return f.fat ? (f.compact ? 16 : 0) + I->prefetch_dist : 0; }
+
+// Where the records will live -- decided on its own, in front of build_op_records, because the launch's form (a list, or records
+// in the arguments) decides which kernel runs it, and the kernel what the records may say (FlushPlan::mixed, bodied)
+static void place_op_records(const Instance *I, FlushPlan &f)
+{
+  const int n_ops = f.n_ops;
+  if (n_ops == 0) return;
+  f.compact = f.fat && compact_list_form(I) && !f.big_cmd();
+  const int kind = slot_kind_of(I, f);
+  for (int sl = 0; sl < I->ops_slots && f.slot_hit < 0; ++sl)
+    if (I->slot_kind[sl] == kind && I->slot_ops[sl].size() == (size_t)n_ops &&
+        memcmp(I->slot_ops[sl].data(), I->pending.data(), sizeof(DevOp) * n_ops) == 0 && I->slot_inl[sl] == I->pending_inl)
+      f.slot_hit = sl;
+  f.in_args = f.slot_hit < 0 && f.fat && (I->soa || I->perm) && I->args_recs && n_ops <= 2;
+}
+
+// Which lane-per-pattern kernel a list is launched with, decided once for the records and the launch alike.  fill_compact_records
+// used to say `mixed` as mix_n4 > 0 && C == 4 && nt_groups == 2 && !ablate, and flush_impl as the line below, read after
+// build_op_records from q.recs_in_args.  Neither was wrong: compact records are built only for a list (n_ops > 0, not in the
+// arguments), mix_n4 > 0 only where C == 4 and nt_groups == 2 (phyhip_create_instance), and `bodied` asks for prefetch_dist == 2
+// itself -- so the two agreed whenever compact records were built.  (An evaluation alone also travels in the arguments: n_ops == 0.)
+static void choose_list_kernel(const Instance *I, FlushPlan &f)
+{
+  f.mixed    = I->mix_n4 > 0 && f.n_ops > 0 && !f.in_args && I->prefetch_dist == 2 && !I->ablate;
+  f.bodied   = I->prefetch_dist == 2 && I->nt_groups >= 2 && (f.mixed || nt2_bodied(I->C, I->nt_groups, f.has_inl));
+  f.soa_grid = f.mixed ? I->mix_n2 + I->mix_n4 : I->grid_nt2;
+}
+
+// The step plan of this launch (phyhip_step_plan.hpp), made when the first reader asks -- a list found in a device slot is not
+// planned again unless its traffic is counted.  Nothing is allocated for one or two records, and a list's plan reuses the
+// instance's storage.
+static const StepPlan *step_plan(Instance *I, FlushPlan &f)
+{
+  if (f.plan) return f.plan;
+  const int n_rec = padded_records(f.n_ops);
+  StepPlan *out = f.plan_short;
+  if (n_rec > 2) { I->step_plan.resize((size_t)n_rec); out = I->step_plan.data(); }
+  plan_steps(I->pending.data(), f.n_ops, I->pending_inl.empty() ? (const InlineDef *)nullptr : I->pending_inl.data(), I->tips, f.window, kPadBits, n_rec, out);
+  return f.plan = out;
 }
 
 // The queued operations as the kernel reads them: in a device slot (a list identical to one still sitting there -- repeated
@@ -463,21 +510,13 @@ static int fill_compact_records(Instance *I, const FlushPlan &f, NtIssue *ir, Nt
 static int build_op_records(Instance *I, FlushPlan &f, TreeParams &q)
 {
   const int  n_ops = f.n_ops;
-  const bool fat = f.fat;
+  const bool fat = f.fat, compact = f.compact, in_args = f.in_args;
   q.last_dest = -1;
   if (n_ops == 0) return 0;
-  // (a slot's kind: 0 DevOps, 1 / 2 descriptor records with loads that many operations ahead, 16 + that: compact records.  A
-  // command for the large-grid resident workgroups reads descriptors)
-  const bool   compact = fat && compact_list_form(I) && !f.big_cmd();
-  const int    kind = fat ? (compact ? 16 : 0) + I->prefetch_dist : 0, n_rec = n_ops + (n_ops & 1);
+  const int    kind = slot_kind_of(I, f), n_rec = padded_records(n_ops), hit = f.slot_hit;
   const size_t ib = (compact ? sizeof(NtIssue) : sizeof(IssueRec)) * n_rec, xb = (compact ? sizeof(NtExec) : sizeof(ExecRec)) * n_rec;
-  int          hit = -1, rc = 0;
-  for (int sl = 0; sl < I->ops_slots && hit < 0; ++sl)
-    if (I->slot_kind[sl] == kind && I->slot_ops[sl].size() == (size_t)n_ops &&
-        memcmp(I->slot_ops[sl].data(), I->pending.data(), sizeof(DevOp) * n_ops) == 0 && I->slot_inl[sl] == I->pending_inl)
-      hit = sl;
-  const bool in_args = hit < 0 && fat && (I->soa || I->perm) && I->args_recs && n_ops <= 2;
-  char      *dst = I->d_ops + (size_t)(hit >= 0 ? hit : I->ops_slot) * I->ops_slot_bytes;
+  int          rc = 0;
+  char        *dst = I->d_ops + (size_t)(hit >= 0 ? hit : I->ops_slot) * I->ops_slot_bytes;
   int        new_slot = -1;
   if (hit < 0)
   {
@@ -495,9 +534,9 @@ static int build_op_records(Instance *I, FlushPlan &f, TreeParams &q)
     if (!fat) memcpy(st, I->pending.data(), bytes);
     else if (compact && !in_args)
     {
-      if ((rc = fill_compact_records(I, f, reinterpret_cast<NtIssue *>(st), reinterpret_cast<NtExec *>((char *)st + ib), n_rec))) return rc;
+      if ((rc = fill_compact_records(I, f, step_plan(I, f), reinterpret_cast<NtIssue *>(st), reinterpret_cast<NtExec *>((char *)st + ib), n_rec))) return rc;
     }
-    else fill_records(I, f, in_args ? q.arg_ir : reinterpret_cast<IssueRec *>(st), in_args ? q.arg_xr : reinterpret_cast<ExecRec *>((char *)st + ib), n_rec);
+    else fill_records(I, f, step_plan(I, f), in_args ? q.arg_ir : reinterpret_cast<IssueRec *>(st), in_args ? q.arg_xr : reinterpret_cast<ExecRec *>((char *)st + ib), n_rec);
     if (in_args) { q.recs_in_args = 1; q.n_real_ops = n_ops; }
     else HIPCHK(hipMemcpyAsync(dst, st, bytes, hipMemcpyHostToDevice, I->stream)); // (reading short lists straight from the pinned staging memory instead was measured: no gain)
   }
@@ -760,26 +799,20 @@ static int prof_end(Instance *I, hipEvent_t (&ev)[2], int n_queued)
 }
 
 // Minimum traffic of this launch if nothing but the kernel's own register forwarding saved a byte: every result is
-// written once; a child is read unless it is a tip (1 byte per pattern) or the result of one of the previous two
-// operations (forwarded in registers -- exactly the flags computed for the operation records, child_descs).
-static void account_traffic(Instance *I, const EdgeEval *ee, const FlushPlan &f)
+// written once; a child is read unless it is a tip (1 byte per pattern) or forwarded in registers -- the reaches of the very
+// step plan the operation records were written from.  (The pad of an odd list is not counted: it moves what its operation moved.)
+static void account_traffic(Instance *I, const EdgeEval *ee, FlushPlan &f)
 {
-  const int    n_ops = f.n_ops;
-  const bool   fat = f.fat;
-  const double rec = (double)I->C * I->S * 8.0 + 4.0;
-  double       rd = 0.0, wr = 0.0;
+  const int       n_ops = f.n_ops;
+  const bool      fat = f.fat;
+  const double    rec = (double)I->C * I->S * 8.0 + 4.0;
+  const double    bytes_of[5] = {1.0, 0.0, 0.0, 2.0 /* (an in-step child: its two tip bytes) */, rec}; // by Reach
+  const StepPlan *plan = n_ops > 0 ? step_plan(I, f) : nullptr;
+  double          rd = 0.0, wr = 0.0;
   for (int k = 0; k < n_ops; ++k)
   {
-    const DevOp &o  = I->pending[k];
-    if (!(o.pad & kOpNoStore)) wr += rec;
-    const int    e1 = k >= 1 ? I->pending[k - 1].dest : -1;
-    const int    e2 = (k >= 2 && fat && I->prefetch_dist == 2) ? I->pending[k - 2].dest : -1;
-    for (int w = 0; w < 2; ++w)
-    {
-      const int c = w ? o.c2 : o.c1;
-      if (o.pad & (w ? kOpInl2 : kOpInl1)) rd += 2.0; // (an in-step child: its two tip bytes)
-      else rd += c < I->tips ? 1.0 : ((fat && (c == e1 || c == e2)) ? 0.0 : rec);
-    }
+    if (plan[k].stored) wr += rec;
+    for (int w = 0; w < 2; ++w) rd += bytes_of[(int)plan[k].reach[w]];
   }
   if (ee)
   { // root edge: both sides unless just produced, pattern weight in; per-pattern outputs out
@@ -1052,10 +1085,12 @@ static int flush_impl(Instance *I, const EdgeEval *ee)
   const unsigned long long hp0 = hp_now();
   FlushPlan f;
   f.n_queued = (int)I->pending.size();
+  f.fat      = ((I->S == 4) && !I->generic_nt) || I->perm;
   // virtual buffers: what the queue reads of them is (re)computed in front of its reader; a long list of the two pipelined
-  // kernels with two-deep register forwarding leaves its own tip x tip results virtual (rewrite_pending)
-  rewrite_pending(I, ee, (I->soa || I->perm) && !I->generic_nt && I->prefetch_dist == 2 && !I->class_axis && !I->generic_loop &&
-                             !(I->ablate & ~8) && !I->no_loads); // (PHYHIP_ABLATE=8 stamps the list a default traversal runs)
+  // kernels leaves results unstored as far as their register window reaches (rewrite_pending: two-deep forwarding)
+  const bool unstoring = (I->soa || I->perm) && !I->generic_nt && !I->class_axis && !I->generic_loop && !(I->ablate & ~8) &&
+                         !I->no_loads; // (PHYHIP_ABLATE=8 stamps the list a default traversal runs)
+  rewrite_pending(I, ee, unstoring ? reg_window(I, f.fat, false) : RegWindow{0});
   I->unstored.keep_clear();
   const int n_ops = f.n_ops = (int)I->pending.size();
   int       rc = 0;
@@ -1069,13 +1104,13 @@ static int flush_impl(Instance *I, const EdgeEval *ee)
   // ---- the kernel arguments: matrices, operation records, evaluation ----
   TreeParams q = base_params(I);
   f.ro      = base_ro(I, nullptr);
-  f.fat     = ((I->S == 4) && !I->generic_nt) || I->perm;
   f.has_inl = !I->pending_inl.empty();
+  f.window  = reg_window(I, f.fat, f.big_cmd());
   fill_matrix_args(I, f, q);
   plan_aa_ring(I, ee, f, q);
+  place_op_records(I, f);
+  choose_list_kernel(I, f);
   if ((rc = build_op_records(I, f, q))) return rc;
-  f.mixed    = I->mix_n4 > 0 && n_ops > 0 && !q.recs_in_args && I->prefetch_dist == 2 && !I->ablate;
-  f.soa_grid = f.mixed ? I->mix_n2 + I->mix_n4 : I->grid_nt2;
   if (ee) setup_evaluation(I, ee, f, q);
 
   // ---- resident workgroups that take the evaluation without a launch, in the order they are tried ----

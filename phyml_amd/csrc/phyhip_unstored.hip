@@ -134,8 +134,8 @@ static bool list_chains(const Instance *I, const std::vector<DevOp> &L, const st
 }
 
 // Deferred buffers, the rule (on the list as it will be launched, front to back): a storing operation whose destination is written
-// once in the list, read in it only by the next two operations -- exactly the reads child_descs forwards in registers -- and
-// neither read by the evaluation nor asked for from memory (keep_real) does not store, if each child is a tip or a buffer that is
+// once in the list, read in it only inside the kernel's register window (`win`; phyhip_step_plan.hpp: the reads the step plan
+// calls Prev1 / Prev2) and neither read by the evaluation nor asked for from memory (keep_real) does not store, if each child is a tip or a buffer that is
 // in memory after this launch: not virtual, not computed in-step, not deferred, not written again behind the operation.  So every
 // deferred definition is made as ONE step over stored inputs, and in a list that does not chain it stays so: no recursion and no
 // order among definitions.
@@ -146,7 +146,7 @@ static bool list_chains(const Instance *I, const std::vector<DevOp> &L, const st
 // result deferred by the first pass may see one of its stored inputs chained by the second (it is one of that input's two readers):
 // then the deferred definition reads an unstored buffer too, and its sequence number is renewed so that the definitions of the
 // list are numbered in list order, inputs before dependants (store_definition follows the inputs of both classes).
-static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> &L, bool chain)
+static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> &L, bool chain, RegWindow win)
 {
   Unstored        &u = I->unstored;
   const int        n = (int)L.size();
@@ -159,8 +159,6 @@ static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> 
     if (o.c1 >= I->tips && !(o.pad & kOpInl1)) last_read[o.c1] = k;
     if (o.c2 >= I->tips && !(o.pad & kOpInl2)) last_read[o.c2] = k;
   }
-  // (the padded re-run of an odd list's last operation: the result three positions back is no longer in registers)
-  const int pad_read1 = (n & 1) ? L[n - 1].c1 : -1, pad_read2 = (n & 1) ? L[n - 1].c2 : -1;
   auto in_memory = [&](int c, bool in_step, int i) {
     return c < I->tips || (!in_step && u.class_of(c) != U::kVirtual && u.class_of(c) != U::kDeferred && last_write[c] < i);
   };
@@ -171,23 +169,23 @@ static void defer_forwarded(Instance *I, const EdgeEval *ee, std::vector<DevOp> 
       DevOp &o = L[i];
       if (pass == 1 && (o.pad & kOpNoStore) && u.class_of(o.dest) == U::kDeferred) u.renew(o.dest); // (deferred by pass 0)
       if ((o.pad & kOpNoStore) || n_dest[o.dest] != 1) continue;
-      if (last_read[o.dest] <= i || last_read[o.dest] > i + 2) continue; // (never read behind it, or read from memory)
+      if (!reads_stay_in_registers(win, i, last_read[o.dest])) continue; // (never read behind it, or read from memory)
       if ((ee && (ee->parent == o.dest || ee->child == o.dest)) || u.kept(o.dest)) continue;
       if (pass == 0 && (!in_memory(o.c1, o.pad & kOpInl1, i) || !in_memory(o.c2, o.pad & kOpInl2, i))) continue;
       if (pass == 1 && (!not_rewritten(o.c1, i) || !not_rewritten(o.c2, i))) continue;
-      if (i + 3 == n && (pad_read1 == o.dest || pad_read2 == o.dest)) continue; // (the odd-list rule, for this class)
+      if (pad_reads_from_memory(win, L.data(), n, i)) continue; // (the odd-list rule, for this class)
       u.make(pass == 0 ? U::kDeferred : U::kChained, o.dest, o);
       o.pad |= kOpNoStore;
     }
 }
 
 // The queue as it will be launched.  Short lists (or kernels without two-deep forwarding): the first one that reads a virtual
-// buffer gets the storing definitions of ALL virtual buffers in front of it.  Long lists (may_virtualise): a tip x tip operation
+// buffer gets the storing definitions of ALL virtual buffers in front of it.  Long lists (a window of depth 2): a tip x tip operation
 // whose result is written once in this list, read only later in it and not by the evaluation leaves its place; every reader of a
 // virtual buffer -- one left virtual by this list or by an earlier one -- computes it inside its own step (one per operation:
 // DevOp::pad bits 1-2, pending_inl) or gets the definition re-issued in front of it, not storing (the kernels forward the
 // results of the previous two operations in registers); what the evaluation edge reads is stored.
-void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
+void rewrite_pending(Instance *I, const EdgeEval *ee, RegWindow forwarding)
 {
   Unstored &u = I->unstored;
   I->pending_inl.clear();
@@ -197,7 +195,8 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
   // (only launches of the LIST form: one- and two-operation launches -- records in the kernel arguments, the resident evaluators --
   // run kernels without in-step children and without the second forwarding level's guarantees: a list must keep three
   // operations even if each of its tip x tip operations leaves its place)
-  bool virtualise = may_virtualise && u.virt_min_ops > 0 && n0 >= u.virt_min_ops && n0 >= 3;
+  // (depth 2: two non-storing re-issues in front of one reader lean on the second forwarding level)
+  bool virtualise = forwarding.depth == 2 && u.virt_min_ops > 0 && n0 >= u.virt_min_ops && n0 >= 3;
   if (virtualise)
   {
     int stay = 0;
@@ -287,20 +286,20 @@ void rewrite_pending(Instance *I, const EdgeEval *ee, bool may_virtualise)
   for (int b : u.keep_real) store_now(b);
   if (ee)
     for (int side : {ee->parent, ee->child}) store_now(side);
-  // The pipelined kernels pad an odd list by running its last operation once more (flush_impl), at a position where the result
-  // of the operation THREE steps back is no longer in registers: a child of the last operation produced there is then read from
-  // memory -- so it must have been stored (two non-storing re-issues in front of a reader; reachable without in-step children)
-  if ((L.size() & 1) && L.size() >= 3)
+  // The pipelined kernels pad an odd list by running its last operation once more (phyhip_step_plan.hpp), at a position where the
+  // result at the far end of the last operation's window is no longer in registers: a child of the last operation produced there
+  // is then read from memory -- so it must have been stored (two non-storing re-issues in front of a reader; reachable without
+  // in-step children)
+  if (const int far = (int)L.size() - 1 - forwarding.depth; far >= 0)
   {
-    DevOp       &d1 = L[L.size() - 3];
-    const DevOp &rd = L.back();
-    if ((d1.pad & kOpNoStore) && (rd.c1 == d1.dest || rd.c2 == d1.dest))
+    DevOp &d1 = L[far];
+    if ((d1.pad & kOpNoStore) && pad_reads_from_memory(forwarding, L.data(), (int)L.size(), far))
     {
       d1.pad &= ~kOpNoStore;
       if (is_virtual(d1.dest)) u.end(d1.dest, U::kMaterial);
     }
   }
-  if (u.defer_stores) defer_forwarded(I, ee, L, list_chains(I, L, LI));
+  if (u.defer_stores) defer_forwarded(I, ee, L, list_chains(I, L, LI), forwarding);
   I->pending.swap(L);
   if (any_inl) I->pending_inl.swap(LI);
   // (the rewritten list is launched as it stands: flush_impl.  A SHORT list leaves here as it came, its stored definitions still

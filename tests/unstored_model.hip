@@ -5,7 +5,9 @@
 // queue with the kernels' forwarding rules (last two results in registers, in-step children, non-storing operations) on symbolic
 // values, in lockstep with the plain semantics (every operation stored, in queue order):
 //   * a stale buffer must never be read from memory; the evaluation edge sees the plain semantics' values;
-//   * what a launch leaves in memory -- or unstored, through its definition -- must be what the plain semantics hold for that buffer.
+//   * what a launch leaves in memory -- or unstored, through its definition -- must be what the plain semantics hold for that buffer;
+//   * the step plan of the rewritten queue (phyhip_step_plan.hpp: what the record encoders read) must say of every child what this
+//     interpretation says of it, register for register, and must load nothing that is stale.
 // The first argument is the highest class of unstored buffer switched on; the checks and events that depend on it:
 //   1  virtual.  Every written buffer is stored or virtual.
 //   2  + deferred (Unstored::defer_stores).  A deferred definition's inputs are in memory and are the plain values they had when the
@@ -99,6 +101,21 @@ struct Model
     const std::vector<DevOp> &L = I->pending;
     const bool has_inl = !I->pending_inl.empty();
     if (has_inl && I->pending_inl.size() != L.size()) die("pending_inl is not parallel to pending");
+    // The step plan the record encoders will read (phyhip_step_plan.hpp), on the rewritten list, against this model's own
+    // interpretation below: a child the plan takes from a register must be that register here, one it loads must not be stale
+    // (said behind the model's own check of the value read, whose wording the controls know).
+    // (Lists of one or two operations travel in the kernel arguments, unpadded: the plan is asked for as many records.)
+    const int n_rec = L.size() >= 3 ? padded_records((int)L.size()) : (int)L.size();
+    std::vector<StepPlan> plan((size_t)n_rec);
+    plan_steps(L.data(), (int)L.size(), has_inl ? I->pending_inl.data() : (const InlineDef *)nullptr, I->tips, RegWindow{2}, kPadBits, n_rec, plan.data());
+    auto against_plan = [&](size_t r, int s, int c, int bit, const DevOp &o, int m1, int m2) {
+      const Reach got = plan[r].reach[s];
+      const Reach own = (o.pad & bit) ? Reach::InStep : c < I->tips ? Reach::Tip : c == m1 ? Reach::Prev1 : c == m2 ? Reach::Prev2 : Reach::Loaded;
+      if (got != own)
+        die((got == Reach::Prev1 || got == Reach::Prev2) ? "the step plan forwards a child that is not the model's register"
+                                                         : "the step plan and the model disagree on how a child reaches its step", c, (int)r);
+      if (plan[r].stored != !(o.pad & 1) || plan[r].op != (int)std::min(r, L.size() - 1)) die("the step plan and the list disagree on a record's operation or store", o.dest, (int)r);
+    };
     int      d1 = -1, d2 = -1; // destinations of the previous two operations
     uint64_t r1 = 0, r2 = 0;   // ... and their results (registers)
     for (size_t k = 0; k < L.size(); ++k)
@@ -123,6 +140,7 @@ struct Model
       }
       auto child = [&](int c, int bit) -> uint64_t {
         uint64_t v;
+        if (!(o.pad & bit) || has_inl) against_plan(k, bit == 4, c, bit, o, d1, d2);
         if (o.pad & bit)
         {
           if (!has_inl) die("in-step flag without a definition", (int)k);
@@ -136,6 +154,7 @@ struct Model
         else if (c == d2) v = r2;
         else v = dev[c];
         if (v != cur[c]) die("an operation reads another value than the plain semantics hold at that point (stale memory, a stale register or a stale definition)", c, (int)k);
+        if (plan[k].reach[bit == 4] == Reach::Loaded && dev[c] != cur[c]) die("the step plan loads a child that is stale in memory", c, (int)k);
         return v;
       };
       const uint64_t v = H(child(o.c1, 2), child(o.c2, 4), matv[o.pm1], matv[o.pm2]);
@@ -155,6 +174,7 @@ struct Model
       ++n_pad;
       auto child = [&](int c, int bit) -> uint64_t {
         uint64_t v;
+        against_plan(L.size(), bit == 4, c, bit, o, d1, d2); // (the pad's own record: d1 is the last operation's own result)
         if (o.pad & bit)
         {
           const InlineDef &d = I->pending_inl[k];
@@ -164,6 +184,7 @@ struct Model
         else if (c == d2) v = r2; // (the operation in front of the last one)
         else v = dev[c];
         if (v != cur[c]) die("the re-run of an odd list's last operation reads a stale value", c, (int)k);
+        if (plan[L.size()].reach[bit == 4] == Reach::Loaded && dev[c] != cur[c]) die("the step plan's padded re-run loads a child that is stale in memory", c, (int)k);
         return v;
       };
       const uint64_t v = H(child(o.c1, 2), child(o.c2, 4), matv[o.pm1], matv[o.pm2]);

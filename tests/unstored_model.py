@@ -101,7 +101,7 @@ DEFECTS = {
     "input": replace_once("    if (needed || (!dead && (written(u.def(b).c1) || written(u.def(b).c2)))) m0.push_back(b);\n",
                           "    if (needed) m0.push_back(b);\n"),
     # defer_forwarded without the odd-list rule
-    "defer_pad": replace_once("      if (i + 3 == n && (pad_read1 == o.dest || pad_read2 == o.dest)) continue; // (the odd-list rule, for this class)\n", ""),
+    "defer_pad": replace_once("      if (pad_reads_from_memory(win, L.data(), n, i)) continue; // (the odd-list rule, for this class)\n", ""),
     # the definitions in front of the queue in DESCENDING sequence order
     "reverse": replace_once("u.seq(I->pending[at].dest) < u.seq(buf)", "u.seq(I->pending[at].dest) > u.seq(buf)"),
     # rewrite_pending forgets the stored definitions in front of the queue every time it runs
